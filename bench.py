@@ -9,11 +9,16 @@ launcher) every rank decodes its own 100M-row row group (row groups shard
 one-per-GPU, no data-path collective: weak scaling); value = all ranks' values /
 max-over-ranks time.
 
-Prints ONE JSON line on rank 0. Extra objects: "roofline" (dominant kernel
-k_dict<8>, HBM-bound), "cpu_baseline" (the oracle's value-at-a-time port of
-the reference reader, 1 thread, bounded sample) and, at N=1, "e2e_host_path" (the
-PCIe-inclusive pqg_decode_host rate with the pinned D2H link ceiling measured in the
-same run; never `value`).
+Prints ONE JSON line on rank 0. A plain run generates the inputs, uploads them,
+launches the fresh plan once, warms up, times `--steps` launches and prints the line:
+nothing is checked and nothing else is measured. `--dump-outputs DIR` also writes what
+the last timed step decoded (see dump_outputs). `--full` adds everything else, each with a run of its own: the check of
+the first launch and of the final state against the generated values, "roofline"'s
+measured traffic and live store ceiling (dominant kernel k_dict<8>, HBM-bound),
+"cpu_baseline" (the oracle's value-at-a-time port of the reference reader, 1 thread,
+bounded sample), at N=1 "e2e_host_path" (the PCIe-inclusive pqg_decode_host rate with
+the pinned D2H link ceiling measured in the same run; never `value`) and at N>1 the
+timed all-gather of the decoded column.
 """
 import argparse
 import json
@@ -29,6 +34,8 @@ sys.path[:0] = [os.path.join(REPO, "parquet-mr_amd"), os.path.join(REPO, "tools"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec)
 DOMINANT_KERNEL = "void pqg::k_dict_fused<8>"
 TRAFFIC_JSON = os.path.join(REPO, "profiles", "traffic_latest.json")
+DUMP_BUDGET = 48_000_000  # bytes of array data that --dump-outputs writes at the most, all files together
+DUMP_SEED = 1234
 
 
 def workload_key(rows, zipf):
@@ -236,6 +243,60 @@ def step_time(gpu_s, wall_s):
     return wall_s, "host wall clock (the HIP event interval exceeded it)"
 
 
+def sample_positions(n, k, seed):
+    """k or fewer sorted positions in [0, n): the first, the last, and seeded uniform draws between
+    them (the same for every run with the same n, k and seed)."""
+    idx = np.random.default_rng(seed).integers(0, n, size=k - 2, dtype=np.int64)
+    return np.unique(np.concatenate([idx, np.array([0, n - 1], dtype=np.int64)]))
+
+
+def column_arrays(cols, batch):
+    """-> [(name, 1-D device tensor)]: what a caller of the plan holds after a launch, per column
+    `colNN_values` (BYTE_ARRAY: `colNN_offsets` and `colNN_bytes`) and, where the column has them,
+    `colNN_def` / `colNN_rep` levels."""
+    from pqgpu import abi
+    out = []
+    for i, (col, cd) in enumerate(zip(cols, batch.columns)):
+        if cd["physical_type"] == abi.BYTE_ARRAY:
+            offs = col.offsets()
+            out.append((f"col{i:02d}_offsets", offs))
+            out.append((f"col{i:02d}_bytes", col.binary_data[: int(offs[-1].item())]))
+        else:
+            out.append((f"col{i:02d}_values", col.typed().reshape(-1)))
+        for name, lv in (("def", col.def_levels), ("rep", col.rep_levels)):
+            if lv is not None:
+                out.append((f"col{i:02d}_{name}", lv.reshape(-1)))
+    return out
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """--dump-outputs: write each (name, device tensor) as out_dir/<name>.npy (ranks above 0 of a
+    multi-GPU run: <name>.rank<r>.npy). float32 stays float32, every other type is written as
+    float64; an int64 array, which float64 cannot hold exactly, also gets <name>_hi32 (value >> 32)
+    and <name>_lo32 (value & 0xffffffff), which together are exact. An array too long for its share
+    of DUMP_BUDGET is sampled at sample_positions (gathered on the device), so two builds given the
+    same arguments write the same elements."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n_files = sum(3 if t.dtype == torch.int64 else 1 for _, t in arrays)
+    per_file = max(DUMP_BUDGET // 8 // max(n_files, 1), 2)  # elements; every file budgeted at 8 B each
+    suffix = f".rank{rank}" if world > 1 and rank > 0 else ""
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+    for k, (name, t) in enumerate(arrays):
+        if t.numel() > per_file:
+            t = t[torch.from_numpy(sample_positions(t.numel(), per_file, DUMP_SEED + k)).to(t.device)]
+        h = t.cpu().numpy()
+        if h.dtype == np.int64:
+            save(name, h.astype(np.float64))
+            save(name + "_hi32", (h >> 32).astype(np.float64))
+            save(name + "_lo32", (h & 0xFFFFFFFF).astype(np.float64))
+        else:
+            save(name, h if h.dtype == np.float32 else h.astype(np.float64))
+
+
 def run_c4(args, world, rank, devi):
     """C4 (BASELINE configs[3]): TPC-H lineitem-shaped 16 columns, `--rows` rows in total (default 1 B)
     in row groups of 1M rows, sharded over the ranks by encoded bytes (dist.shard_row_groups, the
@@ -273,13 +334,15 @@ def run_c4(args, world, rank, devi):
                 t.fill_(0xA5)
     plan = dec.plan(dbatch, cols)
 
+    check = args.full and not args.no_verify
+
     def verify(what):
         shard.verify(cols, dec.device, what)
 
-    plan.launch()  # first launch of the fresh plan, checked
+    plan.launch()  # first launch of the fresh plan (--full: checked)
     rc, st = plan.sync()
     assert rc == 0, st.message
-    if not args.no_verify:
+    if check:
         verify("first launch")
     for _ in range(args.warmup):
         plan.launch()
@@ -300,7 +363,9 @@ def run_c4(args, world, rank, devi):
     wall = time.perf_counter() - t0
     rc, st = plan.sync()
     assert rc == 0, st.message
-    if not args.no_verify:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, column_arrays(cols, batch), rank, world)
+    if check:
         verify("after the timed launches")
     per_launch_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.steps)]
     gpu_s = sum(per_launch_ms) / 1e3
@@ -324,7 +389,7 @@ def run_c4(args, world, rank, devi):
     total_rows, total_bytes = float(rows_all[0].item()), float(rows_all[1].item())
 
     gather = None
-    if world > 1 and not args.no_gather:
+    if args.full and world > 1 and not args.no_gather:
         # final concatenation of two representative columns over RCCL: l_orderkey (int64, fixed width)
         # and l_comment (BYTE_ARRAY: byte-total all-gather + offset rebase), timed separately
         counts = [rg_rows] * n_rg
@@ -351,7 +416,7 @@ def run_c4(args, world, rank, devi):
                   "note": "timed separately; not part of value (decode-only rate)"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         sys.path.insert(0, REPO)
         from oracle import pqref
         b1 = writer.build_batch([templates[0][0][k] for k in shard.keep])
@@ -371,7 +436,7 @@ def run_c4(args, world, rank, devi):
         # tools/c4_traffic.sh) when it was measured on this workload
         c4_traffic, c4_traffic_bytes, c4_traffic_src = None, None, None
         tj_path = os.path.join(REPO, "profiles", "traffic_c4_latest.json")
-        if os.path.exists(tj_path) and world == 1:
+        if args.full and os.path.exists(tj_path) and world == 1:
             tj = json.load(open(tj_path))
             if tj.get("rows") == int(total_rows) and tj.get("columns") == list(shard.keep):
                 c4_traffic_bytes = tj["traffic_bytes_per_launch"]
@@ -401,7 +466,7 @@ def run_c4(args, world, rank, devi):
                          "traffic_source": c4_traffic_src,
                          "kernel": "whole plan launch (all kernels of the shard)",
                          "algorithmic_bytes_per_launch": total_bytes / world},
-            "verified": None if args.no_verify else "every row group x column slice == its generated values, first launch "
+            "verified": None if not check else "every row group x column slice == its generated values, first launch "
                                                     "of a fresh plan and after the timed launches",
             "cpu_baseline": cpu, "input_gen_s": t_gen,
             "timer": timer, "wall_ms_per_step": float(t[1].item()) * 1e3 / args.steps,
@@ -441,13 +506,20 @@ def main():
     ap.add_argument("--c4-cols", default=None,
                     help="c4 diagnostics: comma-separated lineitem columns to decode (default: all 16)")
     ap.add_argument("--zipf", type=float, default=1.5)
+    ap.add_argument("--full", action="store_true",
+                    help="also check the decoded columns against the generated values and measure the store "
+                         "ceiling, the host path, the CPU baselines and (N > 1) the all-gather; the --no-* "
+                         "options below take single legs out of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step decoded as DIR/<name>.npy (float32 / float64, seeded "
+                         "sample of long arrays, under 64 MB in all)")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the timed RCCL all-gather of the column")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default=None)
     ap.add_argument("--e2e", action="store_true",
-                    help="time the host-bytes-in / host-array-out path (default on at N=1, rank 0)")
+                    help="--full: time the host-bytes-in / host-array-out path (default on at N=1, rank 0)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host path (profiling runs)")
     ap.add_argument("--traffic-json", default=TRAFFIC_JSON,
                     help="rocprofv3 PMC traffic summary of this kernel (tools/pmc_summary.py --json)")
@@ -483,11 +555,14 @@ def main():
     plan = dec.plan(dbatch, cols)
     stream = dec.stream
     exp = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         exp = torch.from_numpy(dict_vals[ids]).to(dec.device)
-        plan.launch()  # the FIRST launch of a fresh plan is checked (not one after warm-up rewrites)
-        rc, st = plan.sync()
-        assert rc == 0, st.message
+    # set-up ends with the first launch of the fresh plan (it loads the code objects), so the timed steps
+    # never hold it, whatever --warmup is; --full checks it (the FIRST launch, not one after warm-up rewrites)
+    plan.launch()
+    rc, st = plan.sync()
+    assert rc == 0, st.message
+    if exp is not None:
         assert torch.equal(cols[0].typed(), exp), "first launch: decoded column differs from the generated values"
     for _ in range(args.warmup):
         plan.launch()
@@ -509,6 +584,8 @@ def main():
     wall = time.perf_counter() - t0
     rc, st = plan.sync()
     assert rc == 0, st.message
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, column_arrays(cols, batch), rank, world)
     if exp is not None:
         assert torch.equal(cols[0].typed(), exp), "after the timed launches: decoded column differs"
     per_launch_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(args.steps)]
@@ -520,7 +597,7 @@ def main():
     t_max, timer = step_time(float(t[0].item()), float(t[1].item()))
 
     gather = None
-    if world > 1 and not args.no_gather:
+    if args.full and world > 1 and not args.no_gather:
         # the final column concatenation (north_star: RCCL/xGMI gather only for it), timed on its own:
         # every rank ends with the full world x rows column; checked by a checksum of checksums
         from pqgpu import dist as pdist
@@ -556,10 +633,10 @@ def main():
     avg_launch_s = float(np.mean(per_launch_ms)) / 1e3
     algo_bytes = n * 8 + data_bytes  # per launch: int64 out + encoded data-page bytes read
     achieved = algo_bytes / avg_launch_s / 1e9
-    st_ceil = store_ceiling(n * 8, cols[0].typed().device, stream)
+    st_ceil = store_ceiling(n * 8, cols[0].typed().device, stream) if args.full else None
 
     e2e = None
-    if rank == 0 and (args.e2e or (world == 1 and not args.no_e2e)):
+    if args.full and rank == 0 and (args.e2e or (world == 1 and not args.no_e2e)):
         times, native_s = [], []
         for _ in range(3):  # best of 3 (the first call also allocates and pins the staging buffers)
             t1 = time.perf_counter()
@@ -591,14 +668,14 @@ def main():
                                   "the pinned output for the caller to read in place)"}}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(batch, n, args.cpu_budget)
         threads = min(16, os.cpu_count() or 1)  # the GPU box's CPU share is 16 cores
         cpu["multi_thread"] = cpu_baseline_mt(chunk, n, threads, args.cpu_budget / 2)
         cpu["pyarrow"] = pyarrow_baseline(dict_vals[ids], args.cpu_budget / 2, threads)
 
     traffic, traffic_bytes, traffic_src = None, None, None
-    if os.path.exists(args.traffic_json):
+    if args.full and os.path.exists(args.traffic_json):
         # HBM bytes per launch of the same kernel from the committed rocprofv3 --pmc passes
         # (tools/pmc_summary.py: FETCH_SIZE x2 + WRITE_SIZE, gfx950 corrections); reported in the
         # unit of `achieved` (bytes per launch / this run's average launch time)
@@ -636,7 +713,7 @@ def main():
                          "traffic_bytes_per_launch": traffic_bytes, "traffic_source": traffic_src,
                          "kernel": "pqg::k_dict_fused<8> (avg_launch_ms: whole plan launch, one dispatch, incl. the ~6 us dispatch-to-dispatch gap)", "algorithmic_bytes_per_launch": algo_bytes,
                          "avg_launch_ms": avg_launch_s * 1e3,
-                         "store_ceiling": st_ceil, "frac_of_store_ceiling": achieved / st_ceil,
+                         "store_ceiling": st_ceil, "frac_of_store_ceiling": achieved / st_ceil if st_ceil else None,
                          "store_ceiling_note": "GB/s of a torch fill_ of the 800 MB output on the same stream, "
                                                "best of 10 (write-only; measured live in this run)"},
             "cpu_baseline": cpu,

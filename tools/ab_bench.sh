@@ -8,7 +8,7 @@ for rep in 1 2; do
   for lib in "$@"; do
     n=$(basename "$lib" .so)
     if [ "$lib" = default ]; then unset PQGPU_LIB; else export PQGPU_LIB=$PWD/$lib; fi
-    timeout -k 10 180 python -u bench.py --no-cpu --steps 50 ${AB_ARGS:-} > "$OUT/$n.$rep.json" 2> "$OUT/$n.$rep.err" \
+    timeout -k 10 180 python -u bench.py --full --no-cpu --steps 50 ${AB_ARGS:-} > "$OUT/$n.$rep.json" 2> "$OUT/$n.$rep.err" \
       || { tail -20 "$OUT/$n.$rep.err"; exit 1; }
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], round(d['value']/1e9,1), 'G/s', round(d['ms_per_step']*1e3,1), 'us')" "$OUT/$n.$rep.json" "$n"
   done

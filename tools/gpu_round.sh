@@ -24,15 +24,15 @@ for s in $STEPS; do
         || { tail -30 "$OUT/smoke.log"; exit 1; }
       tail -2 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 400 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" \
+      timeout -k 10 400 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
         || { tail -30 "$OUT/bench.err"; exit 1; }
       cat "$OUT/bench.json" ;;
     e2e)
-      PQG_HOST_TIMING=1 timeout -k 10 400 python -u bench.py --no-cpu --e2e --steps 5 > "$OUT/bench_e2e.json" 2> "$OUT/bench_e2e.err" \
+      PQG_HOST_TIMING=1 timeout -k 10 400 python -u bench.py --full --no-cpu --e2e --steps 5 > "$OUT/bench_e2e.json" 2> "$OUT/bench_e2e.err" \
         || { tail -30 "$OUT/bench_e2e.err"; exit 1; }
       cat "$OUT/bench_e2e.json" ;;
     bench2)
-      timeout -k 10 400 python -u bench.py --no-cpu --no-e2e --zipf 2.0 > "$OUT/bench_zipf2.json" 2> "$OUT/bench_zipf2.err" \
+      timeout -k 10 400 python -u bench.py --full --no-cpu --no-e2e --zipf 2.0 > "$OUT/bench_zipf2.json" 2> "$OUT/bench_zipf2.err" \
         || { tail -30 "$OUT/bench_zipf2.err"; exit 1; }
       cat "$OUT/bench_zipf2.json" ;;
     suite)
@@ -52,7 +52,7 @@ PY
       python3 tools/kstats.py "$OUT/suiteprof" ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-        python3 bench.py --no-cpu --no-e2e > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
+        python3 bench.py --full --no-cpu --no-e2e > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
         || { tail -30 "$OUT/prof.err"; exit 1; }
       python3 tools/kstats.py "$OUT/prof" ;;
     pmc)
@@ -61,13 +61,13 @@ PY
       for grp in "FETCH_SIZE" "WRITE_SIZE" \
                  "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU"; do
         timeout -s KILL 240 rocprofv3 --pmc $grp --output-format csv -d "$OUT/pmc/pass$i" -o run -- \
-          python3 bench.py --no-cpu --no-e2e --steps 5 --warmup 1 > "$OUT/pmc/pass$i.log" 2>&1 \
+          python3 bench.py --full --no-cpu --no-e2e --steps 5 --warmup 1 > "$OUT/pmc/pass$i.log" 2>&1 \
           || { tail -20 "$OUT/pmc/pass$i.log"; exit 1; }
         i=$((i+1))
       done
       python3 tools/pmc_summary.py "$OUT/pmc" --json "$OUT/traffic.json" || true ;;
     c4)
-      timeout -k 10 600 python3 bench.py --workload c4 --rows 125000000 --steps 10 --warmup 2 > "$OUT/bench_c4.json" \
+      timeout -k 10 600 python3 bench.py --full --workload c4 --rows 125000000 --steps 10 --warmup 2 > "$OUT/bench_c4.json" \
         2> "$OUT/bench_c4.err" || { tail -30 "$OUT/bench_c4.err"; exit 1; }
       cat "$OUT/bench_c4.json" ;;
     router)
@@ -81,7 +81,7 @@ PY
       tail -30 "$OUT/diag_fused.log" ;;
     c4prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/c4prof" -o run -- \
-        python3 bench.py --workload c4 --rows 125000000 --steps 5 --warmup 1 --no-cpu > "$OUT/c4prof.json" \
+        python3 bench.py --full --workload c4 --rows 125000000 --steps 5 --warmup 1 --no-cpu > "$OUT/c4prof.json" \
         2> "$OUT/c4prof.err" || { tail -30 "$OUT/c4prof.err"; exit 1; }
       python3 tools/kstats.py "$OUT/c4prof" ;;
     wlpmc|strpmc)
