@@ -34,7 +34,9 @@
  * No exception crosses this ABI: every function returns a pqg_error code and
  * fills an optional pqg_status.
  *
- * ABI 4 (this version): pqg_page_desc carries the V2 header's num_nulls
+ * ABI 5 (this version): record-level filter2 predicates over decoded columns (pqg_filter_create /
+ * pqg_filter_program / pqg_filter_destroy on the host, pqg_filter_run on the device).
+ * ABI 4: pqg_page_desc carries the V2 header's num_nulls
  * (PQG_PAGE_NULL_COUNT, 56-byte descriptor), pqg_plan_null_hint_fallbacks.
  * ABI 3: per-page errors (pqg_page_errors) so that a failure
  * surfaces in its own column only; the staged host path (pqg_host_input /
@@ -52,7 +54,7 @@
 extern "C" {
 #endif
 
-#define PQG_ABI_VERSION 4
+#define PQG_ABI_VERSION 5
 
 /* parquet-format `Type` values (parquet.thrift). */
 enum pqg_physical_type {
@@ -640,6 +642,114 @@ enum pqg_codec {
 int pqg_pages_from_headers(const pqg_page_header* headers, int n_headers, int codec, uint64_t chunk_offset,
                            int column, pqg_column_desc* col, pqg_page_desc* pages, int capacity, int* n_pages,
                            pqg_status* st);
+
+/* ---- record filter (filter2 predicates over decoded columns) ---------------------
+ * Record-level evaluation of a parquet-mr FilterPredicate (filter2/predicate/FilterApi.java) over the
+ * dense columns pqg_decode wrote, on the device: what FilterCompat.FilterPredicateCompat makes
+ * FilteringRecordMaterializer do value by value through IncrementallyUpdatedFilterPredicate
+ * (filter2/recordlevel/IncrementallyUpdatedFilterPredicateEvaluator.java:45-61 and the generated
+ * ValueInspectors, parquet-generator/.../IncrementallyUpdatedFilterPredicateGenerator.java:198-327).
+ * Flat columns only (max_rep == 0); a row is null when its definition level is below max_def, and a
+ * column no value reached (missing from the file) is null in every row.
+ *
+ * The predicate is an array of nodes in post-order (children before parents, one root: the last
+ * node; every other node is the child of exactly one node). pqg_filter_create validates it and
+ * applies LogicalInverseRewriter (filter2/predicate/LogicalInverseRewriter.java,
+ * LogicalInverter.java:56-114) as FilterCompat.get does: not() is pushed down to the leaves
+ * (eq<->notEq, lt<->gtEq, ltEq<->gt, in<->notIn, and<->or), so the program the device runs has no
+ * NOT. That is observable: not(lt(x, 5)) is gtEq(x, 5), false on a null row.
+ *
+ * Leaves compare with the column's PrimitiveComparator (schema/PrimitiveComparator.java:68-207):
+ * Boolean.compare; signed int32 / int64, or unsigned with PQG_FILTER_UNSIGNED (UINT_32 / UINT_64);
+ * Float.compare / Double.compare (a total order: -0.0 < 0.0, every NaN equal and above +Infinity);
+ * unsigned lexicographic bytes then length for BYTE_ARRAY. Null rows: eq / lt / ltEq / gt / gtEq / in
+ * are false and notEq / notIn true; eq(c, null) holds on null rows only, notEq(c, null) on the others;
+ * an in / notIn set containing null behaves as eq / notEq(c, null) (the reference ignores its other
+ * members). PQG_ERR_UNSUPPORTED at creation: INT96 and FIXED_LEN_BYTE_ARRAY columns; programs over
+ * the limits below. PQG_ERR_INVALID_ARG: lt / ltEq / gt / gtEq on BOOLEAN (IllegalArgumentException in
+ * the reference) or against null, a malformed table. */
+#define PQG_FILTER_TILE_ROWS 4096          /* rows per device tile (one wave; a multiple of 64) */
+#define PQG_FILTER_MAX_NODES 64            /* nodes of the rewritten program */
+#define PQG_FILTER_MAX_LITERALS 4096       /* literal cells */
+#define PQG_FILTER_MAX_LITERAL_BYTES 16384 /* BYTE_ARRAY literal bytes */
+
+enum pqg_filter_op {
+  PQG_FILTER_EQ = 0,
+  PQG_FILTER_NOTEQ = 1,
+  PQG_FILTER_LT = 2,
+  PQG_FILTER_LTEQ = 3,
+  PQG_FILTER_GT = 4,
+  PQG_FILTER_GTEQ = 5,
+  PQG_FILTER_IN = 6,
+  PQG_FILTER_NOTIN = 7,
+  PQG_FILTER_AND = 8,
+  PQG_FILTER_OR = 9,
+  PQG_FILTER_NOT = 10
+};
+
+#define PQG_FILTER_NULL_LITERAL 1 /* eq / notEq: the literal is null; in / notIn: the set contains null */
+#define PQG_FILTER_UNSIGNED 2     /* INT32 / INT64 column annotated UINT_32 / UINT_64: unsigned order */
+
+typedef struct pqg_filter_node {
+  int32_t op;             /* pqg_filter_op */
+  int32_t column;         /* leaves: index into column_types / the pqg_filter_column table */
+  int32_t left;           /* AND / OR / NOT: child node (smaller index); leaves: -1 */
+  int32_t right;          /* AND / OR: second child; otherwise -1 */
+  uint32_t flags;         /* PQG_FILTER_* */
+  uint32_t literal_begin; /* leaves: first literal cell */
+  uint32_t n_literals;    /* eq .. gtEq: 1 (0 with PQG_FILTER_NULL_LITERAL); in / notIn: the set's non-null members */
+  uint32_t reserved;      /* 0 (sizeof(pqg_filter_node) = 32) */
+} pqg_filter_node;
+
+typedef struct pqg_filter pqg_filter;
+
+/* Host only (no device, no ctx). A literal cell holds the raw value bits in 8 bytes: BOOLEAN 0 / 1,
+ * INT32 / FLOAT in the low 4 bytes, INT64 / DOUBLE all 8; BYTE_ARRAY: offset | length << 32 into
+ * `literal_bytes`. column_types[c] is the pqg_physical_type of column c. The filter keeps copies of
+ * everything it needs. Sets of more than 8 members are sorted by comparator order for the device's
+ * binary search. */
+int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* column_types, int n_cols,
+                      const uint64_t* literals, int n_literals, const uint8_t* literal_bytes,
+                      uint64_t n_literal_bytes, pqg_filter** out, pqg_status* st);
+/* The rewritten, NOT-free program in post-order (literal_begin indexes the filter's own literal table).
+ * Writes min(cap, count) nodes and returns the count; -1 without a filter. */
+int pqg_filter_program(const pqg_filter* filter, pqg_filter_node* out, int cap);
+int pqg_filter_destroy(pqg_filter* filter);
+
+/* One decoded column as pqg_decode left it. max_def == 0: a required column, row r is values[r].
+ * max_def > 0: def_levels holds one byte per row and values the dense non-null values in row order;
+ * def_levels == NULL then means a column missing from the file (every row null; values unused).
+ * BYTE_ARRAY: values = int64 offsets[n_values + 1] into binary_data (value i is bytes
+ * [offsets[i], offsets[i + 1]), which must be readable: the offsets are the decoder's own). */
+typedef struct pqg_filter_column {
+  int32_t physical_type;       /* pqg_physical_type, equal to the filter's column_types[c] */
+  int32_t max_def;
+  const void* values;          /* device */
+  const uint8_t* binary_data;  /* device, BYTE_ARRAY only */
+  const uint8_t* def_levels;   /* device, may be NULL */
+  uint64_t n_values;           /* dense values behind `values` */
+} pqg_filter_column;
+
+/* Device-resident outcome of one pqg_filter_run. */
+typedef struct pqg_filter_result {
+  uint64_t n_selected;   /* rows the predicate holds on, whatever row_ids_capacity is */
+  int32_t error;         /* PQG_OK, or PQG_ERR_INVALID_ARG: a nullable column's rows with dl == max_def
+                            differ in number from its n_values (the outputs are then undefined) */
+  int32_t error_column;  /* the first such column, -1 without an error */
+} pqg_filter_result;
+
+/* Evaluate `filter` on rows [0, n_rows) of `cols` (host array of n_cols entries, the filter's n_cols;
+ * only the columns the predicate names are read). Asynchronous on the ctx stream; every output is a
+ * DEVICE pointer. d_bitmap: ceil(n_rows / 64) words, row r = bit r & 63 of word r >> 6, the bits past
+ * n_rows in the last word 0. d_row_ids (may be NULL): the selected rows ascending, the first
+ * row_ids_capacity of them. Every value load is checked against n_values: a wrong n_values gives
+ * d_result->error, never a read outside the column. n_rows == 0 is valid.
+ * Five launches, none of which waits on another workgroup: per-tile non-null counts of the nullable
+ * columns, their scan (one workgroup per column), the evaluation, the scan of the tiles' selected
+ * counts, the row ids. */
+int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols, int n_cols,
+                   uint64_t n_rows, uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity,
+                   pqg_filter_result* d_result);
 
 /* Human-readable name of an error code. */
 const char* pqg_error_name(int code);

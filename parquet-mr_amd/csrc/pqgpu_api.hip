@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "pqgpu_internal.h"
+#include "pqgpu_filter.h"
 
 using pqg::ColumnDev;
 using pqg::PageWork;
@@ -253,6 +254,9 @@ struct pqg_ctx {
   bool null_hints = true;   // PQG_DISPATCH_NULL_HINTS
   uint32_t gz_prepass_min = pqg::GZ_PREPASS_MIN;  // PQG_DISPATCH_GZIP_PREPASS_MIN
   RouterCache router;  // pqg_router_read_page
+  // pqg_filter_run: per-tile counts, and the device image of the filter uploaded last (by its serial)
+  DevBuf filter_scratch, filter_image;
+  uint64_t filter_serial = 0;
 };
 
 extern "C" {
@@ -361,6 +365,8 @@ int pqg_ctx_destroy(pqg_ctx* c) {
   c->zstd_mode.release();
   c->gzip_recs.release();
   c->gzip_mode.release();
+  c->filter_scratch.release();
+  c->filter_image.release();
   if (c->copy_stream) {
     (void)hipStreamSynchronize(c->copy_stream);
     (void)hipStreamDestroy(c->copy_stream);
@@ -2077,6 +2083,57 @@ int pqg_unpack_runs(pqg_ctx* ctx, int bit_width, const uint8_t* d_in, const uint
   // the kernel grid-strides inside each run; 64 blocks x 256 lanes per run
   hipError_t e = pqg::launch_unpack_runs(ctx->stream, bit_width, d_in, ~0ull >> 1, d_in_offsets, d_counts, d_out_offsets,
                                          d_out, n_runs, 1u << 14);
+  return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+// ---- record filter (pqgpu_filter_host.cpp builds the filter, pqgpu_filter.hip runs it) -----------
+static_assert(sizeof(pqg_filter_node) == 32 && sizeof(pqg_filter_column) == 40 && sizeof(pqg_filter_result) == 16,
+              "filter ABI layout");
+
+int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols, int n_cols, uint64_t n_rows,
+                   uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result) {
+  if (!ctx || !filter || !d_result || n_cols != (int)filter->column_types.size() || (n_cols > 0 && !cols))
+    return PQG_ERR_INVALID_ARG;
+  if (n_rows && !d_bitmap) return PQG_ERR_INVALID_ARG;
+  pqg::FilterCols fc{};
+  fc.n_slots = (uint32_t)filter->slot_column.size();
+  for (uint32_t s = 0; s < fc.n_slots; s++) {
+    const int col = filter->slot_column[s];
+    const pqg_filter_column& c = cols[col];
+    if (c.physical_type != filter->column_types[(size_t)col] || c.max_def < 0 || c.max_def > 254) return PQG_ERR_INVALID_ARG;
+    const bool missing = c.max_def > 0 && !c.def_levels;
+    if (!missing) {
+      if (!c.values && (c.n_values || c.physical_type == PQG_BYTE_ARRAY)) return PQG_ERR_INVALID_ARG;
+      if (c.physical_type == PQG_BYTE_ARRAY && !c.binary_data) return PQG_ERR_INVALID_ARG;
+      if (c.max_def == 0 && c.n_values < n_rows) return PQG_ERR_INVALID_ARG;  // a required column has a value per row
+    }
+    pqg::FilterColDev& d = fc.c[s];
+    d.values = c.values;
+    d.binary = c.binary_data;
+    d.dl = c.max_def > 0 ? c.def_levels : nullptr;
+    d.n_values = c.n_values;
+    d.type = c.physical_type;
+    d.max_def = c.max_def;
+    d.column = col;
+    d.null_idx = -1;
+    if (d.dl) {
+      d.null_idx = (int32_t)fc.n_nullable;
+      fc.null_slot[fc.n_nullable++] = (uint8_t)s;
+    }
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
+  if (ctx->filter_scratch.ensure(8 * (size_t)pqg::filter_scratch_words(n_rows, fc.n_nullable)) != hipSuccess) return PQG_ERR_HIP;
+  if (ctx->filter_serial != filter->serial) {
+    if (ctx->filter_image.ensure(filter->image.size()) != hipSuccess) return PQG_ERR_HIP;
+    ctx->filter_serial = 0;
+    if (hipMemcpyAsync(ctx->filter_image.p, filter->image.data(), filter->image.size(), hipMemcpyHostToDevice,
+                       ctx->stream) != hipSuccess)
+      return PQG_ERR_HIP;
+    ctx->filter_serial = filter->serial;
+  }
+  const hipError_t e =
+      pqg::launch_filter(ctx->stream, (const uint8_t*)ctx->filter_image.p, (uint32_t)filter->image.size(), fc, n_rows,
+                         (uint64_t*)ctx->filter_scratch.p, d_bitmap, d_row_ids, row_ids_capacity, d_result);
   return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
 }
 

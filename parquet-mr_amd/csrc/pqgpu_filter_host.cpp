@@ -1,0 +1,246 @@
+// pqgpu_filter_host.cpp — host half of the record filter (include/pqgpu.h, "record filter"):
+// validation of a predicate table, LogicalInverseRewriter, literal keys and the device image.
+// Plain C++ with no HIP in it, so that it also builds alone under the sanitizers
+// (tests/c/filter_sanitize.cpp).
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <new>
+
+#include "pqgpu_filter.h"
+
+namespace {
+
+constexpr int kMaxInputNodes = 4096;  // nodes before the rewrite (NOT nodes disappear in it)
+
+int fail(pqg_status* st, int code, int node, const char* msg) {
+  if (st) {
+    st->code = code;
+    st->page = -1;
+    st->value_index = node;
+    snprintf(st->message, sizeof(st->message), "%s", msg);
+  }
+  return code;
+}
+
+bool is_leaf(int op) { return op >= PQG_FILTER_EQ && op <= PQG_FILTER_NOTIN; }
+
+int inverse(int op) {
+  switch (op) {
+    case PQG_FILTER_EQ: return PQG_FILTER_NOTEQ;
+    case PQG_FILTER_NOTEQ: return PQG_FILTER_EQ;
+    case PQG_FILTER_LT: return PQG_FILTER_GTEQ;
+    case PQG_FILTER_GTEQ: return PQG_FILTER_LT;
+    case PQG_FILTER_LTEQ: return PQG_FILTER_GT;
+    case PQG_FILTER_GT: return PQG_FILTER_LTEQ;
+    case PQG_FILTER_IN: return PQG_FILTER_NOTIN;
+    case PQG_FILTER_NOTIN: return PQG_FILTER_IN;
+    case PQG_FILTER_AND: return PQG_FILTER_OR;
+    case PQG_FILTER_OR: return PQG_FILTER_AND;
+    default: return op;
+  }
+}
+
+// Binary.lexicographicCompare (PrimitiveComparator.java:196-207): unsigned bytes, then length.
+int compare_bytes(const uint8_t* a, uint32_t na, const uint8_t* b, uint32_t nb) {
+  const uint32_t n = na < nb ? na : nb;
+  const int c = n ? memcmp(a, b, n) : 0;
+  if (c) return c < 0 ? -1 : 1;
+  return na < nb ? -1 : (na > nb ? 1 : 0);
+}
+
+std::atomic<uint64_t> g_serial{1};
+
+}  // namespace
+
+extern "C" {
+
+int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* column_types, int n_cols,
+                      const uint64_t* literals, int n_literals, const uint8_t* literal_bytes,
+                      uint64_t n_literal_bytes, pqg_filter** out, pqg_status* st) {
+  if (!out) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: out is null");
+  *out = nullptr;
+  if (!nodes || n_nodes <= 0) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no nodes");
+  if (n_cols < 0 || (n_cols > 0 && !column_types)) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no column types");
+  if (n_literals < 0 || (n_literals > 0 && !literals)) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no literal table");
+  if (n_literal_bytes > 0 && !literal_bytes) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no literal bytes");
+  if (n_nodes > kMaxInputNodes) return fail(st, PQG_ERR_UNSUPPORTED, -1, "filter: more than 4096 nodes");
+  if (n_literals > PQG_FILTER_MAX_LITERALS) return fail(st, PQG_ERR_UNSUPPORTED, -1, "filter: more than 4096 literal cells");
+  if (n_literal_bytes > PQG_FILTER_MAX_LITERAL_BYTES)
+    return fail(st, PQG_ERR_UNSUPPORTED, -1, "filter: more than 16 KiB of literal bytes");
+
+  // ---- validation -----------------------------------------------------------------
+  std::vector<int> uses((size_t)n_nodes, 0);
+  for (int i = 0; i < n_nodes; i++) {
+    const pqg_filter_node& nd = nodes[i];
+    if (nd.op < PQG_FILTER_EQ || nd.op > PQG_FILTER_NOT) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown op");
+    if (nd.flags & ~(uint32_t)(PQG_FILTER_NULL_LITERAL | PQG_FILTER_UNSIGNED))
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown flags");
+    if (!is_leaf(nd.op)) {
+      const bool two = nd.op != PQG_FILTER_NOT;
+      if (nd.left < 0 || nd.left >= i) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: child index not below its parent");
+      if (two ? (nd.right < 0 || nd.right >= i || nd.right == nd.left) : nd.right != -1)
+        return fail(st, PQG_ERR_INVALID_ARG, i, "filter: child index not below its parent");
+      uses[(size_t)nd.left]++;
+      if (two) uses[(size_t)nd.right]++;
+      continue;
+    }
+    if (nd.left != -1 || nd.right != -1) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: a leaf has children");
+    if (nd.column < 0 || nd.column >= n_cols) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: column out of range");
+    const int type = column_types[nd.column];
+    if (type < PQG_BOOLEAN || type > PQG_FIXED_LEN_BYTE_ARRAY) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown column type");
+    if (type == PQG_INT96 || type == PQG_FIXED_LEN_BYTE_ARRAY)
+      return fail(st, PQG_ERR_UNSUPPORTED, i, "filter: INT96 / FIXED_LEN_BYTE_ARRAY columns are not supported");
+    if ((nd.flags & PQG_FILTER_UNSIGNED) && type != PQG_INT32 && type != PQG_INT64)
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unsigned order on a column that is not INT32 / INT64");
+    if ((uint64_t)nd.literal_begin + nd.n_literals > (uint64_t)n_literals)
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: literal range past the table");
+    const bool null_lit = (nd.flags & PQG_FILTER_NULL_LITERAL) != 0;
+    const bool set = nd.op == PQG_FILTER_IN || nd.op == PQG_FILTER_NOTIN;
+    const bool ineq = nd.op >= PQG_FILTER_LT && nd.op <= PQG_FILTER_GTEQ;
+    if (ineq && type == PQG_BOOLEAN) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: lt / ltEq / gt / gtEq on a BOOLEAN column");
+    if (ineq && null_lit) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: lt / ltEq / gt / gtEq against null");
+    if (set ? (nd.n_literals == 0 && !null_lit) : nd.n_literals != (null_lit ? 0u : 1u))
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: wrong number of literals");
+    if (type == PQG_BYTE_ARRAY)
+      for (uint32_t k = 0; k < nd.n_literals; k++) {
+        const uint64_t cell = literals[nd.literal_begin + k];
+        if ((cell & 0xFFFFFFFFull) + (cell >> 32) > n_literal_bytes)
+          return fail(st, PQG_ERR_INVALID_ARG, i, "filter: BYTE_ARRAY literal past the literal bytes");
+      }
+  }
+  for (int i = 0; i < n_nodes; i++)
+    if (uses[(size_t)i] != (i == n_nodes - 1 ? 0 : 1))
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: not a tree with its root last");
+
+  // ---- LogicalInverseRewriter -------------------------------------------------------
+  // not(p) is invert(rewrite(p)); inverting twice is the identity on every node kind here, so a node
+  // ends up inverted when an odd number of NOTs stand above it.
+  std::vector<char> inv((size_t)n_nodes, 0);
+  std::vector<int> remap((size_t)n_nodes, -1);
+  for (int i = n_nodes - 1; i >= 0; i--) {
+    const pqg_filter_node& nd = nodes[i];
+    if (nd.op == PQG_FILTER_NOT) {
+      inv[(size_t)nd.left] = !inv[(size_t)i];
+    } else if (!is_leaf(nd.op)) {
+      inv[(size_t)nd.left] = inv[(size_t)nd.right] = inv[(size_t)i];
+    }
+  }
+  pqg_filter* f = new (std::nothrow) pqg_filter();
+  if (!f) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: out of memory");
+  f->serial = g_serial.fetch_add(1);
+  f->column_types.assign(column_types, column_types + n_cols);
+  if (n_literal_bytes) f->bytes.assign(literal_bytes, literal_bytes + n_literal_bytes);
+  for (int i = 0; i < n_nodes; i++) {
+    pqg_filter_node nd = nodes[i];
+    if (nd.op == PQG_FILTER_NOT) {
+      remap[(size_t)i] = remap[(size_t)nd.left];
+      continue;
+    }
+    if (inv[(size_t)i]) nd.op = inverse(nd.op);
+    nd.reserved = 0;
+    if (is_leaf(nd.op)) {
+      const uint32_t begin = (uint32_t)f->cells.size();
+      for (uint32_t k = 0; k < nd.n_literals; k++) f->cells.push_back(literals[nd.literal_begin + k]);
+      nd.literal_begin = begin;
+      if (nd.flags & PQG_FILTER_NULL_LITERAL) {  // the set's other members are ignored
+        f->cells.resize(begin);
+        nd.n_literals = 0;
+      }
+    } else {
+      nd.left = remap[(size_t)nd.left];
+      nd.right = remap[(size_t)nd.right];
+      nd.column = -1;
+      nd.literal_begin = nd.n_literals = 0;
+    }
+    remap[(size_t)i] = (int)f->program.size();
+    f->program.push_back(nd);
+  }
+  if (f->program.size() > PQG_FILTER_MAX_NODES || f->cells.size() > PQG_FILTER_MAX_LITERALS) {
+    delete f;
+    return fail(st, PQG_ERR_UNSUPPORTED, -1, "filter: more than 64 nodes or 4096 literal cells after the rewrite");
+  }
+
+  // ---- sets for the binary search, slots, device image ----------------------------------
+  const uint8_t* lb = f->bytes.data();
+  for (pqg_filter_node& nd : f->program) {
+    if (!is_leaf(nd.op)) continue;
+    const int type = f->column_types[(size_t)nd.column];
+    if (nd.n_literals > pqg::FILTER_IN_LINEAR) {
+      uint64_t* b = f->cells.data() + nd.literal_begin;
+      const bool uns = (nd.flags & PQG_FILTER_UNSIGNED) != 0;
+      if (type == PQG_BYTE_ARRAY)
+        std::sort(b, b + nd.n_literals, [lb](uint64_t x, uint64_t y) {
+          return compare_bytes(lb + (uint32_t)x, (uint32_t)(x >> 32), lb + (uint32_t)y, (uint32_t)(y >> 32)) < 0;
+        });
+      else
+        std::sort(b, b + nd.n_literals, [type, uns](uint64_t x, uint64_t y) {
+          return pqg::filter_key(type, uns, x) < pqg::filter_key(type, uns, y);
+        });
+    }
+    if (std::find(f->slot_column.begin(), f->slot_column.end(), nd.column) == f->slot_column.end())
+      f->slot_column.push_back(nd.column);
+  }
+  pqg::FilterDevHeader h{};
+  h.n_nodes = (uint32_t)f->program.size();
+  h.n_slots = (uint32_t)f->slot_column.size();
+  h.n_cells = (uint32_t)f->cells.size();
+  h.n_bytes = (uint32_t)f->bytes.size();
+  h.cells_off = (uint32_t)(sizeof(h) + h.n_nodes * sizeof(pqg::FilterDevNode) + PQG_FILTER_MAX_NODES);
+  h.bytes_off = h.cells_off + 8u * h.n_cells;
+  h.image_bytes = h.bytes_off + (h.n_bytes + 7u) / 8u * 8u + 8u;
+  f->image.assign(h.image_bytes, 0);
+  uint8_t* img = f->image.data();
+  uint8_t* order = img + sizeof(h) + h.n_nodes * sizeof(pqg::FilterDevNode);
+  for (uint32_t s = 0; s < h.n_slots; s++)
+    for (uint32_t i = 0; i < h.n_nodes; i++) {
+      const pqg_filter_node& nd = f->program[i];
+      if (is_leaf(nd.op) && nd.column == f->slot_column[s]) order[h.n_leaves++] = (uint8_t)i;
+    }
+  for (uint32_t i = 0; i < h.n_nodes; i++) {
+    const pqg_filter_node& nd = f->program[i];
+    pqg::FilterDevNode d{};
+    d.op = (uint8_t)nd.op;
+    d.flags = (uint8_t)nd.flags;
+    if (is_leaf(nd.op)) {
+      const int type = f->column_types[(size_t)nd.column];
+      d.type = (uint8_t)type;
+      d.slot = (uint8_t)(std::find(f->slot_column.begin(), f->slot_column.end(), nd.column) - f->slot_column.begin());
+      d.n_lit = (uint16_t)nd.n_literals;
+      d.lit_begin = nd.literal_begin;
+      for (uint32_t k = 0; k < nd.n_literals; k++) {
+        const uint64_t raw = f->cells[nd.literal_begin + k];
+        const uint64_t cell = type == PQG_BYTE_ARRAY
+                                  ? raw
+                                  : (uint64_t)pqg::filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, raw);
+        memcpy(img + h.cells_off + 8u * (nd.literal_begin + k), &cell, 8);
+      }
+    } else {
+      d.left = (uint8_t)nd.left;
+      d.right = (uint8_t)nd.right;
+    }
+    memcpy(img + sizeof(h) + i * sizeof(d), &d, sizeof(d));
+  }
+  if (h.n_bytes) memcpy(img + h.bytes_off, lb, h.n_bytes);
+  memcpy(img, &h, sizeof(h));
+  *out = f;
+  if (st) fail(st, PQG_OK, -1, "");
+  return PQG_OK;
+}
+
+int pqg_filter_program(const pqg_filter* filter, pqg_filter_node* out, int cap) {
+  if (!filter) return -1;
+  const int n = (int)filter->program.size();
+  if (out)
+    for (int i = 0; i < n && i < cap; i++) out[i] = filter->program[(size_t)i];
+  return n;
+}
+
+int pqg_filter_destroy(pqg_filter* filter) {
+  delete filter;
+  return PQG_OK;
+}
+
+}  // extern "C"

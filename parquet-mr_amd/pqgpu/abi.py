@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # parquet-format Type
 BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY = range(8)
@@ -222,3 +222,36 @@ DISPATCH_DICT_DIRECT = 2
 DISPATCH_GZIP_PREPASS_MIN = 3  # pqg_gzip_decompress: smallest page (output bytes) for the token pre-pass
 DISPATCH_DICT_FUSED = 4  # dictionary pages: 1 = walk + expansion in one launch, 0 = two launches
 DISPATCH_NULL_HINTS = 5  # V2 nullable columns: 1 = value kernels from the header null counts (verified), 0 = levels first
+
+
+# ---- record filter (include/pqgpu.h, "record filter") ----------------------------------------------
+FILTER_TILE_ROWS = 4096          # PQG_FILTER_TILE_ROWS: rows per device tile
+FILTER_MAX_NODES = 64            # nodes of the rewritten program
+FILTER_MAX_LITERALS = 4096       # literal cells
+FILTER_MAX_LITERAL_BYTES = 16384  # BYTE_ARRAY literal bytes
+# pqg_filter_op
+(FILTER_EQ, FILTER_NOTEQ, FILTER_LT, FILTER_LTEQ, FILTER_GT, FILTER_GTEQ, FILTER_IN, FILTER_NOTIN, FILTER_AND,
+ FILTER_OR, FILTER_NOT) = range(11)
+FILTER_NULL_LITERAL = 1  # pqg_filter_node.flags: the literal is null / the set contains null
+FILTER_UNSIGNED = 2      # pqg_filter_node.flags: UINT_32 / UINT_64 order
+
+
+class FilterNode(C.Structure):
+    """pqg_filter_node (32 bytes)."""
+    _fields_ = [("op", C.c_int32), ("column", C.c_int32), ("left", C.c_int32), ("right", C.c_int32),
+                ("flags", C.c_uint32), ("literal_begin", C.c_uint32), ("n_literals", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class FilterColumn(C.Structure):
+    """pqg_filter_column (40 bytes)."""
+    _fields_ = [("physical_type", C.c_int32), ("max_def", C.c_int32), ("values", C.c_void_p),
+                ("binary_data", C.c_void_p), ("def_levels", C.c_void_p), ("n_values", C.c_uint64)]
+
+
+class FilterResult(C.Structure):
+    """pqg_filter_result (16 bytes, device-resident)."""
+    _fields_ = [("n_selected", C.c_uint64), ("error", C.c_int32), ("error_column", C.c_int32)]
+
+
+assert C.sizeof(FilterNode) == 32 and C.sizeof(FilterColumn) == 40 and C.sizeof(FilterResult) == 16

@@ -42,6 +42,8 @@ class DeviceColumn:
         self.rep_levels = rep_levels
         self.binary_data = binary_data  # BYTE_ARRAY: the values' bytes (offsets index into it)
         self.n_values = 0
+        self.max_def = 0 if def_levels is None else 1  # alloc_columns sets the column's own
+        self.flags = 0                                 # pqg_column_desc.flags (COLUMN_DICTIONARY_IDS)
 
     def offsets(self):
         """BYTE_ARRAY: int64 offsets[n_values + 1] (device tensor)."""
@@ -342,6 +344,8 @@ class Decoder:
                     if t is not None:
                         t.fill_(self.poison)
             cols.append(DeviceColumn(cd["physical_type"], vals, dl, rl, cd["type_length"], binary))
+            cols[-1].max_def = int(cd["max_def"])
+            cols[-1].flags = int(cd.get("flags", 0))
         return cols
 
     def _descs(self, batch, cols):
@@ -536,6 +540,43 @@ class Decoder:
                 r["values"] = grab(o.values, n, dt)
             res.append(r)
         return rc, st, res, counts[:batch.n_pages]
+
+    # -- record filter ---------------------------------------------------------------
+    def filter(self, pred, cols, n_rows, row_ids=True, capacity=None, out=None):
+        """Evaluate a filter2 predicate (pqgpu.filter DSL, or a created filter.Filter) on rows
+        [0, n_rows) of the flat columns `cols` (the DeviceColumns decode() returned; a
+        filter.MissingColumn for a column the file does not have). Asynchronous on the decoder's
+        stream (pqg_filter_run); returns a filter.Selection whose `count` / `row_ids` wait for it.
+        capacity: row ids to keep (default n_rows). out: (bitmap int64 tensor, row id int64 tensor or
+        None, 16-byte uint8 result tensor) to write into instead of fresh tensors."""
+        from . import filter as F
+        flt = pred if isinstance(pred, F.Filter) else F.Filter(pred, cols)
+        n_words = (n_rows + 63) // 64
+        capacity = n_rows if capacity is None else int(capacity)
+        if out is not None:
+            words, ids, result = out
+        else:
+            words = torch.empty(max(n_words, 1), dtype=torch.int64, device=self.device)
+            ids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self.device) if row_ids else None
+            result = torch.empty(16, dtype=torch.uint8, device=self.device)
+        arr = (abi.FilterColumn * max(1, len(cols)))()
+        for i, c in enumerate(cols):
+            if getattr(c, "max_rep", 0) or getattr(c, "rep_levels", None) is not None:
+                raise native.PqgError(abi.ERR_UNSUPPORTED, what="filter on a repeated column")
+            arr[i].physical_type = c.physical_type
+            arr[i].max_def = c.max_def
+            arr[i].values = c.values.data_ptr() if c.values is not None else None
+            arr[i].binary_data = c.binary_data.data_ptr() if c.binary_data is not None else None
+            arr[i].def_levels = c.def_levels.data_ptr() if c.def_levels is not None else None
+            arr[i].n_values = c.n_values
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))  # allocations / fills first
+        rc = native.lib().pqg_filter_run(self.ctx, flt.handle, C.addressof(arr), len(cols), n_rows, words.data_ptr(),
+                                         ids.data_ptr() if ids is not None else None, capacity if ids is not None else 0,
+                                         result.data_ptr())
+        native.check(rc, what="pqg_filter_run")
+        sel = F.Selection(self, n_rows, words[:n_words], ids, result, capacity)
+        sel._keep = (flt, cols)
+        return sel
 
     # -- record assembly -------------------------------------------------------------
     def assemble(self, path, n_slots, def_levels=None, rep_levels=None):

@@ -1,0 +1,237 @@
+"""filter2 record predicates over decoded columns: the Python face of pqg_filter_* (include/pqgpu.h).
+
+A small predicate DSL named after parquet-mr's FilterApi (filter2/predicate/FilterApi.java):
+
+    from pqgpu import filter as F
+    pred = F.and_(F.lt_eq(F.col(0), 9_000), F.not_(F.eq(F.col(2), None)))
+    sel = decoder.filter(pred, cols, n_rows)      # cols: the DeviceColumns decode() returned
+    sel.count, sel.bitmap, sel.row_ids
+
+`None` is the null literal (eq / not_eq, or a member of an in_ / not_in set). `compile` flattens a
+predicate to the node, literal and byte tables of the C ABI; `Filter` is the created pqg_filter
+(validated and rewritten without not(), as FilterCompat.get does with LogicalInverseRewriter).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import abi, native
+
+_LEAF_OPS = {"eq": abi.FILTER_EQ, "not_eq": abi.FILTER_NOTEQ, "lt": abi.FILTER_LT, "lt_eq": abi.FILTER_LTEQ,
+             "gt": abi.FILTER_GT, "gt_eq": abi.FILTER_GTEQ, "in": abi.FILTER_IN, "not_in": abi.FILTER_NOTIN}
+OP_NAMES = {v: k for k, v in _LEAF_OPS.items()}
+OP_NAMES.update({abi.FILTER_AND: "and", abi.FILTER_OR: "or", abi.FILTER_NOT: "not"})
+
+
+class Column:
+    """A column of the row group by index; unsigned=True for UINT_32 / UINT_64 annotated columns."""
+
+    def __init__(self, index, unsigned=False):
+        self.index = int(index)
+        self.unsigned = bool(unsigned)
+
+
+class Predicate:
+    """A node of a predicate tree: a leaf (op, column, values) or and / or / not over children."""
+
+    def __init__(self, op, column=None, values=(), children=()):
+        self.op = op
+        self.column = column
+        self.values = tuple(values)
+        self.children = tuple(children)
+
+    def __repr__(self):
+        if self.children:
+            return f"{OP_NAMES[self.op]}({', '.join(map(repr, self.children))})"
+        vals = self.values[0] if self.op < abi.FILTER_IN else set(self.values)
+        return f"{OP_NAMES[self.op]}(col{self.column.index}{'u' if self.column.unsigned else ''}, {vals!r})"
+
+
+def col(index, unsigned=False):
+    return Column(index, unsigned)
+
+
+def _leaf(op, column, values):
+    if not isinstance(column, Column):
+        column = Column(column)
+    return Predicate(op, column, values)
+
+
+def eq(column, value): return _leaf(abi.FILTER_EQ, column, (value,))
+def not_eq(column, value): return _leaf(abi.FILTER_NOTEQ, column, (value,))
+def lt(column, value): return _leaf(abi.FILTER_LT, column, (value,))
+def lt_eq(column, value): return _leaf(abi.FILTER_LTEQ, column, (value,))
+def gt(column, value): return _leaf(abi.FILTER_GT, column, (value,))
+def gt_eq(column, value): return _leaf(abi.FILTER_GTEQ, column, (value,))
+def in_(column, values): return _leaf(abi.FILTER_IN, column, tuple(values))
+def not_in(column, values): return _leaf(abi.FILTER_NOTIN, column, tuple(values))
+def and_(left, right): return Predicate(abi.FILTER_AND, children=(left, right))
+def or_(left, right): return Predicate(abi.FILTER_OR, children=(left, right))
+def not_(pred): return Predicate(abi.FILTER_NOT, children=(pred,))
+
+
+def literal_cell(physical_type, value):
+    """The 8-byte literal cell of a non-null value of a fixed-width type (raw value bits)."""
+    if physical_type == abi.BOOLEAN:
+        return int(bool(value))
+    if physical_type == abi.INT32:
+        return int(value) & 0xFFFFFFFF
+    if physical_type == abi.INT64:
+        return int(value) & 0xFFFFFFFFFFFFFFFF
+    if physical_type == abi.FLOAT:
+        return int(np.asarray(value, dtype=np.float32).reshape(1).view(np.uint32)[0])
+    if physical_type == abi.DOUBLE:
+        return int(np.asarray(value, dtype=np.float64).reshape(1).view(np.uint64)[0])
+    raise native.PqgError(abi.ERR_UNSUPPORTED, what=f"filter literal of type {abi.TYPE_NAMES.get(physical_type)}")
+
+
+class Compiled:
+    """The C ABI tables of a predicate: nodes (post-order, root last), literal cells, literal bytes."""
+
+    def __init__(self, nodes, literals, literal_bytes, column_types):
+        self.nodes = nodes                  # list of (op, column, left, right, flags, literal_begin, n_literals)
+        self.literals = literals            # list of int cells
+        self.literal_bytes = literal_bytes  # bytes
+        self.column_types = column_types    # list of pqg_physical_type
+
+
+def column_types(columns):
+    """Physical types of `columns`: ints, or objects with .physical_type (DeviceColumn, MissingColumn)."""
+    out = []
+    for c in columns:
+        if getattr(c, "flags", 0) & abi.COLUMN_DICTIONARY_IDS:
+            raise native.PqgError(abi.ERR_UNSUPPORTED, what="filter on a column decoded as dictionary ids")
+        out.append(int(getattr(c, "physical_type", c)))
+    return out
+
+
+def compile(pred, columns):
+    """Flatten `pred` (post-order: left, right, node) to the tables pqg_filter_create takes."""
+    types = column_types(columns)
+    nodes, literals, blob = [], [], bytearray()
+
+    def walk(p):
+        if p.children:
+            kids = [walk(k) for k in p.children]
+            nodes.append((p.op, -1, kids[0], kids[1] if len(kids) > 1 else -1, 0, 0, 0))
+            return len(nodes) - 1
+        c = p.column
+        flags = abi.FILTER_UNSIGNED if c.unsigned else 0
+        values = p.values
+        if any(v is None for v in values):
+            flags |= abi.FILTER_NULL_LITERAL
+            values = [v for v in values if v is not None]
+        t = types[c.index] if 0 <= c.index < len(types) else None
+        begin = len(literals)
+        for v in values:
+            if t == abi.BYTE_ARRAY:
+                b = bytes(v)
+                literals.append(len(blob) | (len(b) << 32))
+                blob.extend(b)
+            elif t is None or t in (abi.INT96, abi.FIXED_LEN_BYTE_ARRAY):
+                literals.append(0)  # pqg_filter_create rejects the column
+            else:
+                literals.append(literal_cell(t, v))
+        nodes.append((p.op, c.index, -1, -1, flags, begin, len(values)))
+        return len(nodes) - 1
+
+    walk(pred)
+    return Compiled(nodes, literals, bytes(blob), types)
+
+
+def create(nodes, literals, literal_bytes, types, n_literals=None, n_literal_bytes=None):
+    """pqg_filter_create over raw tables -> (rc, handle, status). The table sizes may be overridden
+    (tests hand in sizes that disagree with the tables)."""
+    arr = (abi.FilterNode * max(1, len(nodes)))()
+    for i, nd in enumerate(nodes):
+        (arr[i].op, arr[i].column, arr[i].left, arr[i].right, arr[i].flags, arr[i].literal_begin,
+         arr[i].n_literals) = nd
+    lit = np.asarray(literals, dtype=np.uint64) if len(literals) else np.zeros(1, dtype=np.uint64)
+    blob = np.frombuffer(bytes(literal_bytes) + b"\0", dtype=np.uint8)
+    ty = np.asarray(list(types) or [0], dtype=np.int32)
+    h = C.c_void_p()
+    st = abi.Status()
+    rc = native.lib().pqg_filter_create(
+        C.addressof(arr), len(nodes), ty.ctypes.data, len(types), lit.ctypes.data,
+        len(literals) if n_literals is None else n_literals, blob.ctypes.data,
+        len(literal_bytes) if n_literal_bytes is None else n_literal_bytes, C.byref(h), C.byref(st))
+    return rc, h, st
+
+
+class Filter:
+    """A created pqg_filter: `pred` validated and rewritten without not()."""
+
+    def __init__(self, pred, columns):
+        self.compiled = compile(pred, columns)
+        c = self.compiled
+        rc, self.handle, st = create(c.nodes, c.literals, c.literal_bytes, c.column_types)
+        native.check(rc, st, "pqg_filter_create")
+        self.n_cols = len(c.column_types)
+
+    def program(self):
+        """The rewritten program: list of (op, column, left, right, flags, literal_begin, n_literals)."""
+        return program(self.handle)
+
+    def close(self):
+        if self.handle:
+            native.lib().pqg_filter_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def program(handle):
+    out = (abi.FilterNode * abi.FILTER_MAX_NODES)()
+    n = native.lib().pqg_filter_program(handle, C.addressof(out), abi.FILTER_MAX_NODES)
+    return [(o.op, o.column, o.left, o.right, o.flags, o.literal_begin, o.n_literals) for o in out[:n]]
+
+
+class MissingColumn:
+    """A column of the requested schema that the file does not have: null in every row
+    (TestFiltersWithMissingColumns)."""
+
+    def __init__(self, physical_type, max_def=1):
+        self.physical_type = physical_type
+        self.max_def = max(1, int(max_def))
+        self.values = self.def_levels = self.binary_data = None
+        self.n_values = 0
+
+
+class Selection:
+    """Outcome of Decoder.filter: `bitmap` (torch int64 view of the uint64 words: row r is bit r & 63 of
+    word r >> 6), `row_ids` (torch int64, ascending; None when not asked for) and `count`."""
+
+    def __init__(self, decoder, n_rows, words, ids, result, capacity):
+        self._decoder = decoder
+        self.n_rows = n_rows
+        self.bitmap = words
+        self._ids = ids
+        self._result = result
+        self._capacity = capacity
+        self._host = None
+
+    def _sync(self):
+        if self._host is None:
+            self._decoder.stream.synchronize()
+            r = self._result.cpu().numpy()
+            n = int(r[:8].view(np.uint64)[0])
+            err, err_col = (int(x) for x in r[8:16].view(np.int32))
+            if err != abi.OK:
+                raise native.PqgError(err, what=f"pqg_filter_run: column {err_col}: rows with a value differ from n_values")
+            self._host = n
+        return self._host
+
+    @property
+    def count(self):
+        """Rows selected (the full count, whatever the row id capacity); waits for the stream."""
+        return self._sync()
+
+    @property
+    def row_ids(self):
+        if self._ids is None:
+            return None
+        return self._ids[:min(self._sync(), self._capacity)]

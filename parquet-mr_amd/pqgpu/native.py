@@ -30,6 +30,8 @@ EXPORTS = [
     "pqg_vr_read_integer", "pqg_vr_read_long", "pqg_vr_read_float", "pqg_vr_read_double", "pqg_vr_read_bytes",
     "pqg_vr_skip", "pqg_vr_skip_n", "pqg_lr_init_from_page", "pqg_lr_remaining", "pqg_lr_read_integer",
     "pqg_lr_skip", "pqg_java_exception",
+    # record filter (filter2 predicates over decoded columns)
+    "pqg_filter_create", "pqg_filter_program", "pqg_filter_destroy", "pqg_filter_run",
 ]
 
 
@@ -98,6 +100,10 @@ def lib():
         L.pqg_crc32.restype = C.c_uint32
         L.pqg_frame_chunk.argtypes = [vp, u64, C.c_int64, i32, vp, i32, C.POINTER(i32), C.POINTER(abi.Status)]
         L.pqg_pages_from_headers.argtypes = [vp, i32, i32, u64, i32, vp, vp, i32, C.POINTER(i32), C.POINTER(abi.Status)]
+        L.pqg_filter_create.argtypes = [vp, i32, vp, i32, vp, i32, vp, u64, C.POINTER(vp), C.POINTER(abi.Status)]
+        L.pqg_filter_program.argtypes = [vp, vp, i32]
+        L.pqg_filter_destroy.argtypes = [vp]
+        L.pqg_filter_run.argtypes = [vp, vp, vp, i32, u64, vp, vp, u64, vp]
         L.pqg_error_name.argtypes = [i32]
         L.pqg_error_name.restype = C.c_char_p
         if L.pqg_abi_version() != abi.ABI_VERSION:
