@@ -34,7 +34,9 @@
  * No exception crosses this ABI: every function returns a pqg_error code and
  * fills an optional pqg_status.
  *
- * ABI 5 (this version): record-level filter2 predicates over decoded columns (pqg_filter_create /
+ * ABI 6 (this version): the rows a selection bitmap keeps, gathered into compact columns on the
+ * device (pqg_take; PQG_DISPATCH_TAKE_STAGED).
+ * ABI 5: record-level filter2 predicates over decoded columns (pqg_filter_create /
  * pqg_filter_program / pqg_filter_destroy on the host, pqg_filter_run on the device).
  * ABI 4: pqg_page_desc carries the V2 header's num_nulls
  * (PQG_PAGE_NULL_COUNT, 56-byte descriptor), pqg_plan_null_hint_fallbacks.
@@ -54,7 +56,7 @@
 extern "C" {
 #endif
 
-#define PQG_ABI_VERSION 5
+#define PQG_ABI_VERSION 6
 
 /* parquet-format `Type` values (parquet.thrift). */
 enum pqg_physical_type {
@@ -247,6 +249,8 @@ void* pqg_ctx_stream(pqg_ctx* ctx);
  *   PQG_DISPATCH_NULL_HINTS      nullable columns of V2 pages: 1 = value kernels start from the header
  *                                null counts beside the level decode, which verifies them (default;
  *                                PQG_PAGE_NULL_COUNT), 0 = levels first
+ *   PQG_DISPATCH_TAKE_STAGED     pqg_take: 1 = kept values and levels staged in LDS and stored as aligned
+ *                                full-wave runs (default), 0 = one store per kept lane
  *   PQG_DISPATCH_GZIP_PREPASS_MIN pqg_gzip_decompress: pages of at least `value` output bytes take the
  *                                token pre-pass + replay, smaller ones the one-wave decoder (default
  *                                16384; 0 = every page); applies to later pqg_gzip_decompress calls
@@ -256,7 +260,8 @@ enum pqg_dispatch {
   PQG_DISPATCH_DICT_DIRECT = 2,
   PQG_DISPATCH_GZIP_PREPASS_MIN = 3,
   PQG_DISPATCH_DICT_FUSED = 4,
-  PQG_DISPATCH_NULL_HINTS = 5
+  PQG_DISPATCH_NULL_HINTS = 5,
+  PQG_DISPATCH_TAKE_STAGED = 6
 };
 int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value);
 
@@ -750,6 +755,77 @@ typedef struct pqg_filter_result {
 int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols, int n_cols,
                    uint64_t n_rows, uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity,
                    pqg_filter_result* d_result);
+
+/* ---- row selection ------------------------------------------------------------------------------
+ * The last step of decode -> filter -> records: the rows a bitmap keeps, gathered into compact
+ * columns in the decoder's own layout. What is reproduced is what the reference hands back after a
+ * record filter or a column-index skip: RecordReaderImplementation.read drops the records
+ * shouldSkipCurrentRecord names (RecordReaderImplementation.java:440-449,
+ * filter2/recordlevel/FilteringRecordMaterializer.java), and SynchronizingColumnReader skips the rows
+ * outside the RowRanges (column/impl/SynchronizingColumnReader.java,
+ * internal/filter2/columnindex/RowRanges.java). The kept records appear in row order, unchanged: every
+ * column shows exactly the value or null it had. The selection is a bitmap, so the bitmap
+ * pqg_filter_run wrote and a host-built bitmap of row ranges are equally valid inputs.
+ *
+ * Element widths: BOOLEAN 1 byte, INT32 / FLOAT / dictionary ids 4, INT64 / DOUBLE 8, INT96 12,
+ * FIXED_LEN_BYTE_ARRAY type_length. `values` / `out_values` are naturally aligned for 1 / 4 / 8,
+ * 4-byte aligned for INT96, 8-byte aligned for BYTE_ARRAY offsets, unaligned for FIXED_LEN_BYTE_ARRAY. */
+#define PQG_TAKE_MAX_COLUMNS 64 /* columns per call; more -> PQG_ERR_UNSUPPORTED */
+
+typedef struct pqg_take_column {
+  int32_t physical_type;        /* any pqg_physical_type */
+  int32_t max_def;              /* as pqg_filter_column */
+  int32_t type_length;          /* FIXED_LEN_BYTE_ARRAY; 0 otherwise */
+  int32_t flags;                /* PQG_COLUMN_DICTIONARY_IDS: values are uint32 ids (4-byte elements) */
+  const void* values;           /* device, as pqg_decode left it (BYTE_ARRAY: int64 offsets[n_values + 1]) */
+  const uint8_t* binary_data;   /* device, BYTE_ARRAY only */
+  const uint8_t* def_levels;    /* device; NULL with max_def > 0: missing column, every row null */
+  uint64_t n_values;
+  void* out_values;             /* device; BYTE_ARRAY: int64 offsets, out_offsets[0] = 0 */
+  uint8_t* out_binary_data;     /* device, BYTE_ARRAY only */
+  uint8_t* out_def_levels;      /* device, one byte per kept row; NULL allowed when max_def == 0 (a required
+                                   column has no levels: never written) or the column is missing */
+  uint64_t out_values_capacity; /* elements (BYTE_ARRAY: values; out_values holds capacity + 1 offsets) */
+  uint64_t out_binary_capacity; /* bytes */
+} pqg_take_column;
+
+/* Per column, device-resident: the full counts whatever the capacities are. */
+typedef struct pqg_take_counts {
+  uint64_t n_values; /* dense values of the kept rows (a required column: the kept rows) */
+  uint64_t n_bytes;  /* BYTE_ARRAY: bytes of those values; 0 otherwise */
+} pqg_take_counts;
+
+/* Device-resident outcome of one pqg_take. */
+typedef struct pqg_take_result {
+  uint64_t n_rows;      /* kept rows, whatever out_rows_capacity is */
+  int32_t error;        /* PQG_OK, or PQG_ERR_INVALID_ARG: a nullable column's rows with dl == max_def differ
+                           in number from its n_values, or a count exceeds a capacity (kept rows over
+                           out_rows_capacity, which counts against every column; a column's values over
+                           out_values_capacity; its bytes over out_binary_capacity). The outputs are then
+                           undefined, but no byte is written past a stated capacity */
+  int32_t error_column; /* the lowest such column, -1 without an error (or with no columns) */
+} pqg_take_result;
+
+/* Gather the rows of [0, n_rows) whose bit is set in d_bitmap (row r = bit r & 63 of word r >> 6, the
+ * layout pqg_filter_run writes; bits past n_rows in the last word are ignored) into the outputs of
+ * `cols` (host array of n_cols entries). Asynchronous on the ctx stream: after a pqg_filter_run on the
+ * same ctx no synchronisation is needed. Per column, for the kept rows in ascending order:
+ * out_def_levels[j] = the level byte of the j-th kept row; out_values = the dense values of the kept
+ * non-null rows (a required column: one per kept row); BYTE_ARRAY: offsets from 0, bytes packed without
+ * gaps, out_offsets[n_values_out] written also when nothing was kept and no slot past it. A missing
+ * column produces nothing but its counts, which are 0. Every value load is checked against n_values and
+ * every store against the capacities. n_rows == 0 and n_cols == 0 are valid (n_cols == 0: just the
+ * kept-row count). Refused before any launch, PQG_ERR_INVALID_ARG: a NULL ctx / d_counts / d_result,
+ * n_rows > 0 without a bitmap, max_def outside 0..254, FIXED_LEN_BYTE_ARRAY with type_length <= 0, a
+ * misaligned or missing pointer the column needs (values with n_values > 0, offsets and bytes of a
+ * BYTE_ARRAY column, out_values with a capacity, out_def_levels of a nullable column with
+ * out_rows_capacity > 0), a required column with n_values < n_rows; PQG_ERR_UNSUPPORTED: more than
+ * PQG_TAKE_MAX_COLUMNS columns. Repeated columns are out of scope (no repetition levels here).
+ * Launches, none of which waits on another workgroup and whose number does not depend on n_cols: per
+ * (column, tile) counts, their scans, with BYTE_ARRAY columns the kept bytes per tile and their scan,
+ * the verdicts, the gather (one wave per column and tile of PQG_FILTER_TILE_ROWS rows). */
+int pqg_take(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_column* cols, int n_cols,
+             uint64_t out_rows_capacity, pqg_take_counts* d_counts, pqg_take_result* d_result);
 
 /* Human-readable name of an error code. */
 const char* pqg_error_name(int code);

@@ -20,6 +20,7 @@
 
 #include "pqgpu_internal.h"
 #include "pqgpu_filter.h"
+#include "pqgpu_take.h"
 
 using pqg::ColumnDev;
 using pqg::PageWork;
@@ -257,6 +258,14 @@ struct pqg_ctx {
   // pqg_filter_run: per-tile counts, and the device image of the filter uploaded last (by its serial)
   DevBuf filter_scratch, filter_image;
   uint64_t filter_serial = 0;
+  // pqg_take: per-tile counts; the column table on the device and the pinned slots it is copied from
+  // (a slot is reused once the copy out of it has run: its event)
+  static constexpr int TAKE_SLOTS = 4;
+  DevBuf take_scratch, take_cols;
+  PinnedBuf take_pin;
+  hipEvent_t take_ev[TAKE_SLOTS] = {};
+  uint32_t take_seq = 0;
+  bool take_staged = true;  // PQG_DISPATCH_TAKE_STAGED
 };
 
 extern "C" {
@@ -341,6 +350,10 @@ int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value) {
       if (value != 0 && value != 1) return PQG_ERR_INVALID_ARG;
       ctx->null_hints = value != 0;
       return PQG_OK;
+    case PQG_DISPATCH_TAKE_STAGED:
+      if (value != 0 && value != 1) return PQG_ERR_INVALID_ARG;
+      ctx->take_staged = value != 0;
+      return PQG_OK;
     default: return PQG_ERR_INVALID_ARG;
   }
 }
@@ -367,6 +380,11 @@ int pqg_ctx_destroy(pqg_ctx* c) {
   c->gzip_mode.release();
   c->filter_scratch.release();
   c->filter_image.release();
+  c->take_scratch.release();
+  c->take_cols.release();
+  c->take_pin.release();
+  for (hipEvent_t& e : c->take_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->copy_stream) {
     (void)hipStreamSynchronize(c->copy_stream);
     (void)hipStreamDestroy(c->copy_stream);
@@ -2134,6 +2152,46 @@ int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_colu
   const hipError_t e =
       pqg::launch_filter(ctx->stream, (const uint8_t*)ctx->filter_image.p, (uint32_t)filter->image.size(), fc, n_rows,
                          (uint64_t*)ctx->filter_scratch.p, d_bitmap, d_row_ids, row_ids_capacity, d_result);
+  return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+// ---- row selection (pqgpu_take_host.cpp validates, pqgpu_take.hip runs) ---------------------------
+static_assert(sizeof(pqg_take_column) == 88 && sizeof(pqg_take_counts) == 16 && sizeof(pqg_take_result) == 16,
+              "take ABI layout");
+
+int pqg_take(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_column* cols, int n_cols,
+             uint64_t out_rows_capacity, pqg_take_counts* d_counts, pqg_take_result* d_result) {
+  pqg::TakeColDev tab[PQG_TAKE_MAX_COLUMNS];
+  const int rc = pqg::take_validate(ctx != nullptr, d_bitmap, n_rows, cols, n_cols, out_rows_capacity, d_counts, d_result, tab);
+  if (rc != PQG_OK) return rc;
+  bool any_nullable = false, any_binary = false;
+  for (int i = 0; i < n_cols; i++) {
+    any_nullable |= tab[i].dl != nullptr;
+    any_binary |= tab[i].kind == pqg::TAKE_BINARY;
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
+  constexpr size_t slot_bytes = sizeof(tab);
+  if (ctx->take_scratch.ensure(8 * (size_t)pqg::take_scratch_words(n_rows, (uint32_t)n_cols)) != hipSuccess ||
+      ctx->take_cols.ensure(slot_bytes) != hipSuccess || ctx->take_pin.ensure(slot_bytes * pqg_ctx::TAKE_SLOTS) != hipSuccess)
+    return PQG_ERR_HIP;
+  if (n_cols) {
+    const uint32_t slot = ctx->take_seq++ % pqg_ctx::TAKE_SLOTS;
+    hipEvent_t& ev = ctx->take_ev[slot];
+    if (!ev) {
+      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return PQG_ERR_HIP;
+    } else if (hipEventSynchronize(ev) != hipSuccess) {  // the copy out of this slot TAKE_SLOTS calls ago
+      return PQG_ERR_HIP;
+    }
+    void* pin = (uint8_t*)ctx->take_pin.p + slot * slot_bytes;
+    std::memcpy(pin, tab, sizeof(pqg::TakeColDev) * (size_t)n_cols);
+    if (hipMemcpyAsync(ctx->take_cols.p, pin, sizeof(pqg::TakeColDev) * (size_t)n_cols, hipMemcpyHostToDevice, ctx->stream) !=
+            hipSuccess ||
+        hipEventRecord(ev, ctx->stream) != hipSuccess)
+      return PQG_ERR_HIP;
+  }
+  const hipError_t e = pqg::launch_take(ctx->stream, d_bitmap, n_rows, (const pqg::TakeColDev*)ctx->take_cols.p, (uint32_t)n_cols,
+                                        any_nullable, any_binary, out_rows_capacity, (uint64_t*)ctx->take_scratch.p, d_counts,
+                                        d_result, ctx->take_staged);
   return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
 }
 

@@ -95,6 +95,39 @@ __device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t x) {
   return x;
 }
 
+// Exclusive scan in place of a[0, n) by one 256-thread workgroup, PER elements per thread per round;
+// returns the total (in every thread). Call with the whole workgroup.
+template <int PER>
+__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t* __restrict__ a, uint64_t n) {
+  __shared__ uint64_t warp_sums[4];
+  uint64_t carry = 0;
+  for (uint64_t r0 = 0; r0 < n; r0 += 256 * PER) {
+    const uint64_t i0 = r0 + (uint64_t)threadIdx.x * PER;
+    uint64_t v[PER], own = 0;
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+      v[q] = i0 + q < n ? a[i0 + q] : 0;
+      own += v[q];
+    }
+    const uint64_t x = wave_incl_scan_u64(own);
+    if ((threadIdx.x & 63u) == 63) warp_sums[threadIdx.x >> 6] = x;
+    __syncthreads();
+    uint64_t pre = carry + x - own, tot = 0;
+    for (int wv = 0; wv < 4; wv++) {
+      pre += wv < (int)(threadIdx.x >> 6) ? warp_sums[wv] : 0;
+      tot += warp_sums[wv];
+    }
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+      if (i0 + q < n) *(__attribute__((address_space(1))) uint64_t*)&a[i0 + q] = pre;
+      pre += v[q];
+    }
+    carry += tot;
+    __syncthreads();
+  }
+  return carry;
+}
+
 // Mask of bytes [jb, je) (clamped) within dword i of a 16-byte block.
 __device__ __forceinline__ uint32_t block_byte_mask(int32_t jb, int32_t je, int32_t i) {
   const int32_t lo = jb - 4 * i < 0 ? 0 : (jb - 4 * i > 4 ? 4 : jb - 4 * i);

@@ -72,33 +72,7 @@ template <bool FINAL>
 __global__ __launch_bounds__(256) void k_filter_scan(uint64_t* __restrict__ arr, uint64_t n_tiles, const FilterCols cols,
                                                      uint64_t* __restrict__ totals, uint64_t* __restrict__ bad,
                                                      pqg_filter_result* __restrict__ result) {
-  uint64_t* a = arr + (uint64_t)blockIdx.x * n_tiles;
-  __shared__ uint64_t warp_sums[4];
-  uint64_t carry = 0;
-  for (uint64_t r0 = 0; r0 < n_tiles; r0 += 256 * FS_PER) {
-    const uint64_t i0 = r0 + (uint64_t)threadIdx.x * FS_PER;
-    uint64_t v[FS_PER], own = 0;
-#pragma unroll
-    for (int q = 0; q < FS_PER; q++) {
-      v[q] = i0 + q < n_tiles ? a[i0 + q] : 0;
-      own += v[q];
-    }
-    const uint64_t x = wave_incl_scan_u64(own);
-    if (lane_id() == 63) warp_sums[threadIdx.x >> 6] = x;
-    __syncthreads();
-    uint64_t pre = carry + x - own, tot = 0;
-    for (int wv = 0; wv < 4; wv++) {
-      pre += wv < (int)(threadIdx.x >> 6) ? warp_sums[wv] : 0;
-      tot += warp_sums[wv];
-    }
-#pragma unroll
-    for (int q = 0; q < FS_PER; q++) {
-      if (i0 + q < n_tiles) gst(&a[i0 + q], pre);
-      pre += v[q];
-    }
-    carry += tot;
-    __syncthreads();
-  }
+  const uint64_t carry = block_excl_scan_u64<FS_PER>(arr + (uint64_t)blockIdx.x * n_tiles, n_tiles);
   if (threadIdx.x != 0) return;
   if (!FINAL) {
     gst(&totals[blockIdx.x], carry);

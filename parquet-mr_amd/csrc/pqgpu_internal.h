@@ -270,6 +270,15 @@ inline uint64_t filter_scratch_words(uint64_t n_rows, uint32_t n_nullable) {
 hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_bytes, const FilterCols& cols,
                          uint64_t n_rows, uint64_t* scratch, uint64_t* bitmap, int64_t* row_ids, uint64_t row_ids_capacity,
                          pqg_filter_result* result);
+// pqgpu_take.hip: pqg_take. scratch (u64 words): keep[n_tiles], rank[n_cols][n_tiles], kept[n_cols][n_tiles],
+// bytes[n_cols][n_tiles] (per-tile counts, scanned in place), totals[1 + 3 n_cols]
+struct TakeColDev;
+inline uint64_t take_scratch_words(uint64_t n_rows, uint32_t n_cols) {
+  return (1 + 3 * (uint64_t)n_cols) * (filter_tiles(n_rows) + 1);
+}
+hipError_t launch_take(hipStream_t st, const uint64_t* bitmap, uint64_t n_rows, const TakeColDev* d_cols, uint32_t n_cols,
+                       bool any_nullable, bool any_binary, uint64_t rows_capacity, uint64_t* scratch,
+                       pqg_take_counts* counts, pqg_take_result* result, bool staged);
 hipError_t launch_unpack_runs(hipStream_t st, int w, const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
                               const uint32_t* counts, const uint64_t* out_off, int32_t* out, int n_runs,
                               uint32_t max_count);

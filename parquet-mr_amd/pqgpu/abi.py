@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # parquet-format Type
 BOOLEAN, INT32, INT64, INT96, FLOAT, DOUBLE, BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY = range(8)
@@ -221,6 +221,7 @@ DISPATCH_PLAIN_ONE_PASS = 1
 DISPATCH_DICT_DIRECT = 2
 DISPATCH_GZIP_PREPASS_MIN = 3  # pqg_gzip_decompress: smallest page (output bytes) for the token pre-pass
 DISPATCH_DICT_FUSED = 4  # dictionary pages: 1 = walk + expansion in one launch, 0 = two launches
+DISPATCH_TAKE_STAGED = 6  # pqg_take: 1 = kept elements staged in LDS and stored as aligned full-wave runs, 0 = one store per kept lane
 DISPATCH_NULL_HINTS = 5  # V2 nullable columns: 1 = value kernels from the header null counts (verified), 0 = levels first
 
 
@@ -255,3 +256,28 @@ class FilterResult(C.Structure):
 
 
 assert C.sizeof(FilterNode) == 32 and C.sizeof(FilterColumn) == 40 and C.sizeof(FilterResult) == 16
+
+
+# ---- row selection (include/pqgpu.h, "row selection") -----------------------------------------------
+TAKE_MAX_COLUMNS = 64  # PQG_TAKE_MAX_COLUMNS: columns per pqg_take call
+
+
+class TakeColumn(C.Structure):
+    """pqg_take_column (88 bytes)."""
+    _fields_ = [("physical_type", C.c_int32), ("max_def", C.c_int32), ("type_length", C.c_int32), ("flags", C.c_int32),
+                ("values", C.c_void_p), ("binary_data", C.c_void_p), ("def_levels", C.c_void_p), ("n_values", C.c_uint64),
+                ("out_values", C.c_void_p), ("out_binary_data", C.c_void_p), ("out_def_levels", C.c_void_p),
+                ("out_values_capacity", C.c_uint64), ("out_binary_capacity", C.c_uint64)]
+
+
+class TakeCounts(C.Structure):
+    """pqg_take_counts (16 bytes, device-resident, one per column)."""
+    _fields_ = [("n_values", C.c_uint64), ("n_bytes", C.c_uint64)]
+
+
+class TakeResult(C.Structure):
+    """pqg_take_result (16 bytes, device-resident)."""
+    _fields_ = [("n_rows", C.c_uint64), ("error", C.c_int32), ("error_column", C.c_int32)]
+
+
+assert C.sizeof(TakeColumn) == 88 and C.sizeof(TakeCounts) == 16 and C.sizeof(TakeResult) == 16

@@ -578,6 +578,20 @@ class Decoder:
         sel._keep = (flt, cols)
         return sel
 
+    # -- row selection ----------------------------------------------------------------
+    def take(self, selection, cols, n_rows=None, rows_capacity=None, out=None):
+        """Gather the rows a selection keeps into compact columns (pqg_take): what
+        FilteringRecordMaterializer hands back after a record filter, or SynchronizingColumnReader
+        after a RowRanges skip, in the decoder's own layout. selection: the filter.Selection of
+        Decoder.filter (no sync in between), or an int64 bitmap tensor (row r = bit r & 63 of word
+        r >> 6) with n_rows. cols: flat DeviceColumns / filter.MissingColumns. rows_capacity: an upper
+        bound of the kept rows the caller knows (default n_rows; it also bounds every column's values).
+        out: one take.Output per column to write into instead of fresh tensors. Asynchronous on the
+        decoder's stream; returns a take.Taken whose `n_rows` / `columns` wait for it. More than
+        abi.TAKE_MAX_COLUMNS columns are split over several calls."""
+        from . import take as T
+        return T.take(self, selection, cols, n_rows, rows_capacity, out)
+
     # -- record assembly -------------------------------------------------------------
     def assemble(self, path, n_slots, def_levels=None, rep_levels=None):
         """Dremel record assembly of one leaf column (pqg_assemble): `path` = repetitions of the

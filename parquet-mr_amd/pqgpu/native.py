@@ -32,6 +32,8 @@ EXPORTS = [
     "pqg_lr_skip", "pqg_java_exception",
     # record filter (filter2 predicates over decoded columns)
     "pqg_filter_create", "pqg_filter_program", "pqg_filter_destroy", "pqg_filter_run",
+    # row selection (the rows a bitmap keeps, as compact columns)
+    "pqg_take",
 ]
 
 
@@ -104,6 +106,7 @@ def lib():
         L.pqg_filter_program.argtypes = [vp, vp, i32]
         L.pqg_filter_destroy.argtypes = [vp]
         L.pqg_filter_run.argtypes = [vp, vp, vp, i32, u64, vp, vp, u64, vp]
+        L.pqg_take.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
         L.pqg_error_name.argtypes = [i32]
         L.pqg_error_name.restype = C.c_char_p
         if L.pqg_abi_version() != abi.ABI_VERSION:
