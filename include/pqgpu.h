@@ -35,7 +35,9 @@
  * fills an optional pqg_status.
  *
  * ABI 6 (this version): the rows a selection bitmap keeps, gathered into compact columns on the
- * device (pqg_take; PQG_DISPATCH_TAKE_STAGED).
+ * device (pqg_take; PQG_DISPATCH_TAKE_STAGED). Added to ABI 6 without a change to what it had:
+ * record filters on dictionary-id columns (pqg_filter_dictionary, pqg_filter_run_dict,
+ * PQG_FILTER_DICT_LDS_BYTES) and pqg_decode_dictionary.
  * ABI 5: record-level filter2 predicates over decoded columns (pqg_filter_create /
  * pqg_filter_program / pqg_filter_destroy on the host, pqg_filter_run on the device).
  * ABI 4: pqg_page_desc carries the V2 header's num_nulls
@@ -755,6 +757,56 @@ typedef struct pqg_filter_result {
 int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols, int n_cols,
                    uint64_t n_rows, uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity,
                    pqg_filter_result* d_result);
+
+/* ---- record filter on dictionary ids (an addition to ABI 6) --------------------------------------
+ * A leaf's verdict on a dictionary-encoded column depends on the id alone, so the predicate is
+ * evaluated once per dictionary entry and looked up per row: decode ids (PQG_COLUMN_DICTIONARY_IDS),
+ * filter on the ids, pqg_take, and only the kept rows are ever materialised. The reference evaluates
+ * the predicate per value (IncrementallyUpdatedFilterPredicate) and uses the dictionary only to drop
+ * whole row groups (filter2/dictionarylevel/DictionaryFilter.java).
+ *
+ * The decoded dictionary of one filter column, on the device, in the decoder's layout
+ * (fixed width: n_entries elements; BYTE_ARRAY: int64 offsets[n_entries + 1] into binary_data).
+ * values == NULL: the column holds values, as for pqg_filter_run. */
+typedef struct pqg_filter_dictionary {
+  const void* values;
+  const uint8_t* binary_data;
+  uint32_t n_entries;
+  uint32_t reserved;   /* 0; sizeof == 24 */
+} pqg_filter_dictionary;
+
+/* Bytes of verdict tables (one bit per dictionary entry and leaf, whole 64-bit words per leaf) up to
+ * which pqg_filter_run_dict keeps a program's tables in LDS; above it they are read from global memory.
+ * 8 KiB: with a small program (image below 2 KiB) a workgroup then allocates at most 10 KiB, and the 8
+ * workgroups of 4 waves a CU holds at the evaluation kernel's register use still fit its 160 KiB. */
+#define PQG_FILTER_DICT_LDS_BYTES 8192
+
+/* pqg_filter_run with dictionaries: `dicts` is a host array of n_cols entries, or NULL. For a column c
+ * with dicts[c].values != NULL, cols[c].values holds the uint32 ids pqg_decode wrote with
+ * PQG_COLUMN_DICTIONARY_IDS (4-byte aligned), cols[c].n_values counts them and cols[c].physical_type is
+ * the dictionary's type (the filter's column_types[c]); cols[c].binary_data is unused. Everything else
+ * is as for pqg_filter_run, and so are the outputs: bit for bit those of pqg_filter_run on the
+ * materialised column dictionary[ids]. With dicts == NULL or no entry set it is pqg_filter_run.
+ * A row with a value whose id is >= n_entries gives d_result->error = PQG_ERR_DICT_ID with error_column
+ * the lowest such column the predicate names (PQG_ERR_INVALID_ARG from the n_values check takes
+ * precedence); the dictionary is never read outside [0, n_entries). n_entries == 0 is valid (a column
+ * that is null in every row). PQG_ERR_INVALID_ARG before any launch: a dictionary on a missing column,
+ * a BYTE_ARRAY dictionary without binary_data, misaligned ids, non-zero `reserved`.
+ * One launch more than pqg_filter_run when a leaf without a null literal stands on a dictionary column:
+ * first the verdict of every such leaf on every dictionary entry. */
+int pqg_filter_run_dict(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols,
+                        const pqg_filter_dictionary* dicts, int n_cols, uint64_t n_rows, uint64_t* d_bitmap,
+                        int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result);
+
+/* Decode the dictionary page `col` names (dict_offset, dict_size, dict_num_values, dict_encoding,
+ * physical_type, type_length; d_bytes / n_bytes as for pqg_decode) into col->values / col->binary_data
+ * within values_capacity / binary_capacity, any physical type: the PLAIN values of a required column
+ * (PlainValuesDictionary). The levels, max_rep / max_def and flags of `col` are ignored. Errors the
+ * descriptor shows are returned at once (PQG_ERR_NO_DICTIONARY, PQG_ERR_DICT_ENCODING, PQG_ERR_EOF for a
+ * fixed-width page shorter than its entries, capacities); otherwise asynchronous like pqg_decode, which
+ * it counts as: col->values_written and the remaining errors are valid after pqg_sync, and `col` must
+ * stay alive until then. */
+int pqg_decode_dictionary(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_column_desc* col, pqg_status* st);
 
 /* ---- row selection ------------------------------------------------------------------------------
  * The last step of decode -> filter -> records: the rows a bitmap keeps, gathered into compact

@@ -258,6 +258,15 @@ struct pqg_ctx {
   // pqg_filter_run: per-tile counts, and the device image of the filter uploaded last (by its serial)
   DevBuf filter_scratch, filter_image;
   uint64_t filter_serial = 0;
+  // pqg_filter_run_dict: the FilterDictTab on the device and its pinned slots (as take_cols / take_pin)
+  DevBuf filter_dict;
+  PinnedBuf filter_dict_pin;
+  hipEvent_t filter_dict_ev[4] = {};
+  uint32_t filter_dict_seq = 0;
+  // pqg_decode_dictionary: the one-column batch it decodes (last_cols points at dict_desc until the next
+  // decode) and the caller's descriptor that pqg_sync fills from it
+  pqg_column_desc dict_desc = {};
+  pqg_column_desc* dict_user = nullptr;
   // pqg_take: per-tile counts; the column table on the device and the pinned slots it is copied from
   // (a slot is reused once the copy out of it has run: its event)
   static constexpr int TAKE_SLOTS = 4;
@@ -380,6 +389,10 @@ int pqg_ctx_destroy(pqg_ctx* c) {
   c->gzip_mode.release();
   c->filter_scratch.release();
   c->filter_image.release();
+  c->filter_dict.release();
+  c->filter_dict_pin.release();
+  for (hipEvent_t& e : c->filter_dict_ev)
+    if (e) (void)hipEventDestroy(e);
   c->take_scratch.release();
   c->take_cols.release();
   c->take_pin.release();
@@ -1497,6 +1510,24 @@ int sync_plan(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work) {
 
 extern "C" {
 
+// pqg_decode_dictionary decodes a BYTE_ARRAY dictionary page as a PLAIN data page, where an entry that reaches
+// past the page is an EOFException; PlainBinaryDictionary's slice of it is what pqg_decode reports as
+// PQG_ERR_CORRUPT for a dictionary page. Error path only: the page's length prefixes, walked on the host.
+static int dict_page_eof_code(const pqg_plan* P, const pqg_column_desc& user) {
+  std::vector<uint8_t> page(user.dict_size);
+  if (!page.empty() && hipMemcpy(page.data(), P->d_bytes + user.dict_offset, page.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return PQG_ERR_HIP;
+  uint64_t p = 0;
+  for (uint32_t i = 0; i < user.dict_num_values; i++) {
+    if (p + 4 > page.size()) return PQG_ERR_EOF;
+    uint32_t len;
+    std::memcpy(&len, page.data() + p, 4);
+    if ((int32_t)len < 0 || p + 4 + len > page.size()) return PQG_ERR_CORRUPT;
+    p += 4 + (uint64_t)len;
+  }
+  return PQG_ERR_EOF;
+}
+
 int pqg_sync(pqg_ctx* ctx, pqg_status* st) {
   if (st) { std::memset(st, 0, sizeof(*st)); st->page = -1; }
   if (!ctx) return PQG_ERR_INVALID_ARG;
@@ -1516,7 +1547,12 @@ int pqg_sync(pqg_ctx* ctx, pqg_status* st) {
     std::memset(&pst, 0, sizeof(pst));
     pst.page = -1;
     std::vector<PageWork> work;
-    const int prc = sync_plan(P, &pst, &work);
+    int prc = sync_plan(P, &pst, &work);
+    if (prc == PQG_ERR_EOF && P == ctx->last && ctx->dict_user && ctx->last_cols == &ctx->dict_desc &&
+        ctx->dict_desc.physical_type == PQG_BYTE_ARRAY) {
+      prc = dict_page_eof_code(P, *ctx->dict_user);
+      set_status(&pst, prc, -1, pst.value_index, "dictionary page");
+    }
     if (prc != PQG_OK && pst.code == 0 && pst.message[0] == '\0')
       set_status(&pst, prc, -1, -1, prc == PQG_ERR_HIP ? hipGetErrorString(hipGetLastError()) : "plan sync failed");
     if (prc != PQG_OK && rc == PQG_OK) {
@@ -1534,6 +1570,7 @@ int pqg_sync(pqg_ctx* ctx, pqg_status* st) {
         }
         ctx->last_cols[i].values_written = n;
       }
+      if (ctx->dict_user && ctx->last_cols == &ctx->dict_desc) ctx->dict_user->values_written = ctx->dict_desc.values_written;
     }
   }
   ctx->unsynced.clear();
@@ -1577,6 +1614,7 @@ static int decode_impl(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, u
       }
     }
   }
+  ctx->dict_user = nullptr;
   if (ctx->last) {
     pqg_plan_destroy(ctx->last);
     ctx->last = nullptr;
@@ -2108,39 +2146,16 @@ int pqg_unpack_runs(pqg_ctx* ctx, int bit_width, const uint8_t* d_in, const uint
 static_assert(sizeof(pqg_filter_node) == 32 && sizeof(pqg_filter_column) == 40 && sizeof(pqg_filter_result) == 16,
               "filter ABI layout");
 
-int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols, int n_cols, uint64_t n_rows,
-                   uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result) {
-  if (!ctx || !filter || !d_result || n_cols != (int)filter->column_types.size() || (n_cols > 0 && !cols))
-    return PQG_ERR_INVALID_ARG;
-  if (n_rows && !d_bitmap) return PQG_ERR_INVALID_ARG;
-  pqg::FilterCols fc{};
-  fc.n_slots = (uint32_t)filter->slot_column.size();
-  for (uint32_t s = 0; s < fc.n_slots; s++) {
-    const int col = filter->slot_column[s];
-    const pqg_filter_column& c = cols[col];
-    if (c.physical_type != filter->column_types[(size_t)col] || c.max_def < 0 || c.max_def > 254) return PQG_ERR_INVALID_ARG;
-    const bool missing = c.max_def > 0 && !c.def_levels;
-    if (!missing) {
-      if (!c.values && (c.n_values || c.physical_type == PQG_BYTE_ARRAY)) return PQG_ERR_INVALID_ARG;
-      if (c.physical_type == PQG_BYTE_ARRAY && !c.binary_data) return PQG_ERR_INVALID_ARG;
-      if (c.max_def == 0 && c.n_values < n_rows) return PQG_ERR_INVALID_ARG;  // a required column has a value per row
-    }
-    pqg::FilterColDev& d = fc.c[s];
-    d.values = c.values;
-    d.binary = c.binary_data;
-    d.dl = c.max_def > 0 ? c.def_levels : nullptr;
-    d.n_values = c.n_values;
-    d.type = c.physical_type;
-    d.max_def = c.max_def;
-    d.column = col;
-    d.null_idx = -1;
-    if (d.dl) {
-      d.null_idx = (int32_t)fc.n_nullable;
-      fc.null_slot[fc.n_nullable++] = (uint8_t)s;
-    }
-  }
+static_assert(sizeof(pqg_filter_dictionary) == 24, "filter dictionary ABI layout");
+
+// The launches of pqg_filter_run / pqg_filter_run_dict once pqg::filter_bind has accepted the columns.
+static int filter_launch(pqg_ctx* ctx, const pqg_filter* filter, const pqg::FilterCols& fc, const pqg::FilterDictTab* dt,
+                         uint64_t n_rows, uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity,
+                         pqg_filter_result* d_result) {
   if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
-  if (ctx->filter_scratch.ensure(8 * (size_t)pqg::filter_scratch_words(n_rows, fc.n_nullable)) != hipSuccess) return PQG_ERR_HIP;
+  const uint64_t dict_words = dt ? PQG_FILTER_MAX_NODES + dt->table_words : 0;
+  if (ctx->filter_scratch.ensure(8 * (size_t)pqg::filter_scratch_words(n_rows, fc.n_nullable, dict_words)) != hipSuccess)
+    return PQG_ERR_HIP;
   if (ctx->filter_serial != filter->serial) {
     if (ctx->filter_image.ensure(filter->image.size()) != hipSuccess) return PQG_ERR_HIP;
     ctx->filter_serial = 0;
@@ -2149,10 +2164,94 @@ int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_colu
       return PQG_ERR_HIP;
     ctx->filter_serial = filter->serial;
   }
+  if (dt) {
+    // the dictionary table goes up like pqg_take's column table: through a pinned slot that is reused
+    // once the copy out of it has run
+    constexpr size_t slot_bytes = sizeof(pqg::FilterDictTab);
+    if (ctx->filter_dict.ensure(slot_bytes) != hipSuccess || ctx->filter_dict_pin.ensure(slot_bytes * pqg_ctx::TAKE_SLOTS) != hipSuccess)
+      return PQG_ERR_HIP;
+    const uint32_t slot = ctx->filter_dict_seq++ % pqg_ctx::TAKE_SLOTS;
+    hipEvent_t& ev = ctx->filter_dict_ev[slot];
+    if (!ev) {
+      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return PQG_ERR_HIP;
+    } else if (hipEventSynchronize(ev) != hipSuccess) {
+      return PQG_ERR_HIP;
+    }
+    void* pin = (uint8_t*)ctx->filter_dict_pin.p + slot * slot_bytes;
+    std::memcpy(pin, dt, slot_bytes);
+    if (hipMemcpyAsync(ctx->filter_dict.p, pin, slot_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipEventRecord(ev, ctx->stream) != hipSuccess)
+      return PQG_ERR_HIP;
+  }
   const hipError_t e =
       pqg::launch_filter(ctx->stream, (const uint8_t*)ctx->filter_image.p, (uint32_t)filter->image.size(), fc, n_rows,
-                         (uint64_t*)ctx->filter_scratch.p, d_bitmap, d_row_ids, row_ids_capacity, d_result);
+                         (uint64_t*)ctx->filter_scratch.p, d_bitmap, d_row_ids, row_ids_capacity, d_result,
+                         dt ? (const pqg::FilterDictTab*)ctx->filter_dict.p : nullptr, dt);
   return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+int pqg_filter_run(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols, int n_cols, uint64_t n_rows,
+                   uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result) {
+  if (!ctx || !filter || !d_result) return PQG_ERR_INVALID_ARG;
+  if (n_rows && !d_bitmap) return PQG_ERR_INVALID_ARG;
+  pqg::FilterCols fc;
+  const int rc = pqg::filter_bind(filter, cols, nullptr, n_cols, n_rows, &fc, nullptr, nullptr);
+  if (rc != PQG_OK) return rc;
+  return filter_launch(ctx, filter, fc, nullptr, n_rows, d_bitmap, d_row_ids, row_ids_capacity, d_result);
+}
+
+int pqg_filter_run_dict(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_column* cols,
+                        const pqg_filter_dictionary* dicts, int n_cols, uint64_t n_rows, uint64_t* d_bitmap,
+                        int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result) {
+  if (!ctx || !filter || !d_result) return PQG_ERR_INVALID_ARG;
+  if (n_rows && !d_bitmap) return PQG_ERR_INVALID_ARG;
+  pqg::FilterCols fc;
+  pqg::FilterDictTab dt;
+  bool any_dict = false;
+  const int rc = pqg::filter_bind(filter, cols, dicts, n_cols, n_rows, &fc, &dt, &any_dict);
+  if (rc != PQG_OK) return rc;
+  return filter_launch(ctx, filter, fc, any_dict ? &dt : nullptr, n_rows, d_bitmap, d_row_ids, row_ids_capacity, d_result);
+}
+
+int pqg_decode_dictionary(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_column_desc* col, pqg_status* st) {
+  if (st) { std::memset(st, 0, sizeof(*st)); st->page = -1; }
+  if (!ctx || !col) return PQG_ERR_INVALID_ARG;
+  int err = PQG_OK;
+  const int ew = elem_width(col->physical_type, col->type_length);
+  // the checks pqg_decode makes of a column's dictionary page, in its order (PlainValuesDictionary)
+  if (col->dict_offset < 0) err = PQG_ERR_NO_DICTIONARY;
+  else if (col->dict_encoding != PQG_PLAIN && col->dict_encoding != PQG_PLAIN_DICTIONARY) err = PQG_ERR_DICT_ENCODING;
+  else if (col->physical_type == PQG_FIXED_LEN_BYTE_ARRAY && col->type_length <= 0) err = PQG_ERR_CORRUPT;
+  else if ((uint64_t)col->dict_offset + col->dict_size > n_bytes) err = PQG_ERR_INVALID_ARG;
+  else if (col->physical_type == PQG_BOOLEAN ? ((uint64_t)col->dict_num_values + 7) / 8 > col->dict_size
+                                             : ew > 0 && (uint64_t)col->dict_num_values * (uint64_t)ew > col->dict_size)
+    err = PQG_ERR_EOF;
+  if (err) {
+    set_status(st, err, -1, -1, "dictionary page");
+    return err;
+  }
+  // a dictionary page is the PLAIN values of a required column: one V1 page of a one-column batch
+  pqg_column_desc& d = ctx->dict_desc;
+  d = *col;
+  d.max_rep = d.max_def = 0;
+  d.dict_offset = -1;
+  d.dict_size = d.dict_num_values = 0;
+  d.flags = 0;
+  d.def_levels = d.rep_levels = nullptr;
+  d.levels_capacity = 0;
+  d.values_written = 0;
+  pqg_page_desc g;
+  std::memset(&g, 0, sizeof(g));
+  g.offset = (uint64_t)col->dict_offset;
+  g.size = col->dict_size;
+  g.num_values = col->dict_num_values;
+  g.column = 0;
+  g.version = 1;
+  g.encoding = PQG_PLAIN;
+  g.rl_encoding = g.dl_encoding = PQG_RLE;
+  const int rc = decode_impl(ctx, d_bytes, n_bytes, n_bytes, &d, 1, &g, 1, nullptr, st);
+  if (rc == PQG_OK) ctx->dict_user = col;  // pqg_sync hands values_written on
+  return rc;
 }
 
 // ---- row selection (pqgpu_take_host.cpp validates, pqgpu_take.hip runs) ---------------------------

@@ -615,7 +615,10 @@ __global__ __launch_bounds__(256) void k_gather_fixed(const uint8_t* __restrict_
   const uint64_t nb = (uint64_t)uni(pw.n_values) * W;
   const uint32_t* ids = cd.blen + pw.out_offset;
   uint8_t* out = (uint8_t*)cd.values + pw.out_offset * W;
-  const rsrc_t drs = make_rsrc(bytes + cd.dict_offset, cd.dict_bytes);
+  // whole dwords: a buffer load is range-checked per dword, so the last 1-3 bytes of a page whose size is
+  // no multiple of 4 would read as 0 (the batch buffer is padded past its last page, inside n_bytes)
+  const uint64_t dwords = (cd.dict_bytes + 3) & ~3ull, left = n_bytes - cd.dict_offset;
+  const rsrc_t drs = make_rsrc(bytes + cd.dict_offset, dwords < left ? dwords : left);
   for (uint64_t o = lane_id(); o < nb; o += WAVE) {
     const uint32_t i = (uint32_t)(o / W), k = (uint32_t)(o % W);
     const uint32_t id = ids[i];

@@ -33,6 +33,53 @@ struct FilterDevHeader {
 
 constexpr uint32_t FILTER_IN_LINEAR = 8;  // sets up to this size are probed linearly, larger ones by binary search
 
+// The columns the program reads (its slots), passed to the kernels by value; null_slot lists the
+// slots that have definition levels (the columns k_filter_rank counts).
+struct FilterColDev {
+  const void* values;    // dense values, or the uint32 ids of a column that has a dictionary (FilterDictSlot)
+  const uint8_t* binary;
+  const uint8_t* dl;     // null: required (max_def == 0) or missing (max_def > 0)
+  uint64_t n_values;
+  int32_t type;
+  int32_t max_def;
+  int32_t column;        // the caller's column index (error_column)
+  int32_t null_idx;      // position in null_slot, -1 without definition levels
+};
+struct FilterCols {
+  uint32_t n_slots, n_nullable;
+  uint8_t null_slot[PQG_FILTER_MAX_NODES];
+  FilterColDev c[PQG_FILTER_MAX_NODES];
+};
+
+// pqg_filter_run_dict: what the kernels need beyond FilterCols, read from a small device table (FilterCols
+// with these fields in it would pass the 4 KiB of kernel arguments).
+struct FilterDictSlot {
+  const void* values;     // the slot's dictionary in the decoder's layout; its ids are FilterColDev::values
+  const uint8_t* binary;
+  uint32_t n_entries;
+  uint32_t is_dict;       // 0: the slot holds values
+};
+constexpr uint64_t FILTER_NO_TABLE = ~0ull;
+struct FilterDictTab {
+  uint32_t n_tables;      // leaves with a verdict table of at least one word (k_filter_dict's grid.y)
+  uint32_t in_lds;        // the tables are staged in LDS behind the image (table_words * 8 <= PQG_FILTER_DICT_LDS_BYTES)
+  uint64_t table_words;   // u64 words of all tables: ceil(n_entries / 64) per table
+  uint64_t max_words;     // the largest table (k_filter_dict's grid.x covers it)
+  uint64_t leaf_off[PQG_FILTER_MAX_NODES];   // node -> first word of its table, FILTER_NO_TABLE without one
+  uint8_t table_leaf[PQG_FILTER_MAX_NODES];  // t-th table -> node
+  FilterDictSlot slot[PQG_FILTER_MAX_NODES];
+};
+// image + staged tables stay inside the 64 KiB a workgroup may allocate
+static_assert(sizeof(FilterDevHeader) + PQG_FILTER_MAX_NODES * (sizeof(FilterDevNode) + 1) + 8 * PQG_FILTER_MAX_LITERALS +
+                      PQG_FILTER_MAX_LITERAL_BYTES + 16 + PQG_FILTER_DICT_LDS_BYTES <= 65536,
+              "filter image + dictionary tables exceed a workgroup's LDS");
+
+// Binds the caller's columns (and dictionaries, or null) to the program's slots: every refusal
+// pqg_filter_run / pqg_filter_run_dict make before a launch, the FilterCols the kernels take and, with
+// dictionaries, the FilterDictTab (`dt` may be null without them). No device calls.
+int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const pqg_filter_dictionary* dicts, int n_cols,
+                uint64_t n_rows, FilterCols* fc, FilterDictTab* dt, bool* any_dict);
+
 }  // namespace pqg
 
 struct pqg_filter {

@@ -1,7 +1,8 @@
 // pqgpu_filter_host.cpp — host half of the record filter (include/pqgpu.h, "record filter"):
-// validation of a predicate table, LogicalInverseRewriter, literal keys and the device image.
+// validation of a predicate table, LogicalInverseRewriter, literal keys and the device image, and the
+// binding of a run's columns and dictionaries to the program's slots (pqg::filter_bind).
 // Plain C++ with no HIP in it, so that it also builds alone under the sanitizers
-// (tests/c/filter_sanitize.cpp).
+// (tests/c/filter_sanitize.cpp, tests/c/filter_dict_sanitize.cpp).
 #include <stdio.h>
 #include <string.h>
 
@@ -244,3 +245,78 @@ int pqg_filter_destroy(pqg_filter* filter) {
 }
 
 }  // extern "C"
+
+namespace pqg {
+
+int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const pqg_filter_dictionary* dicts, int n_cols,
+                uint64_t n_rows, FilterCols* fc, FilterDictTab* dt, bool* any_dict) {
+  if (any_dict) *any_dict = false;
+  if (!filter || !fc || n_cols != (int)filter->column_types.size() || (n_cols > 0 && !cols)) return PQG_ERR_INVALID_ARG;
+  if (dicts && !dt) return PQG_ERR_INVALID_ARG;
+  memset(fc, 0, sizeof(*fc));
+  if (dt) {
+    memset(dt, 0, sizeof(*dt));
+    for (uint64_t& o : dt->leaf_off) o = FILTER_NO_TABLE;
+  }
+  bool any = false;
+  fc->n_slots = (uint32_t)filter->slot_column.size();
+  for (uint32_t s = 0; s < fc->n_slots; s++) {
+    const int col = filter->slot_column[s];
+    const pqg_filter_column& c = cols[col];
+    if (c.physical_type != filter->column_types[(size_t)col] || c.max_def < 0 || c.max_def > 254) return PQG_ERR_INVALID_ARG;
+    const bool missing = c.max_def > 0 && !c.def_levels;
+    const pqg_filter_dictionary* dc = dicts && dicts[col].values ? &dicts[col] : nullptr;
+    if (dicts && dicts[col].reserved) return PQG_ERR_INVALID_ARG;
+    if (dc) {
+      // the column holds uint32 ids; its values are the dictionary's
+      if (missing) return PQG_ERR_INVALID_ARG;
+      if (c.physical_type == PQG_BYTE_ARRAY && !dc->binary_data) return PQG_ERR_INVALID_ARG;
+      if (((uintptr_t)c.values & 3u) || (!c.values && c.n_values)) return PQG_ERR_INVALID_ARG;
+      if (c.max_def == 0 && c.n_values < n_rows) return PQG_ERR_INVALID_ARG;
+      FilterDictSlot& ds = dt->slot[s];
+      ds.values = dc->values;
+      ds.binary = dc->binary_data;
+      ds.n_entries = dc->n_entries;
+      ds.is_dict = 1;
+      any = true;
+    } else if (!missing) {
+      if (!c.values && (c.n_values || c.physical_type == PQG_BYTE_ARRAY)) return PQG_ERR_INVALID_ARG;
+      if (c.physical_type == PQG_BYTE_ARRAY && !c.binary_data) return PQG_ERR_INVALID_ARG;
+      if (c.max_def == 0 && c.n_values < n_rows) return PQG_ERR_INVALID_ARG;  // a required column has a value per row
+    }
+    FilterColDev& d = fc->c[s];
+    d.values = c.values;
+    d.binary = dc ? nullptr : c.binary_data;
+    d.dl = c.max_def > 0 ? c.def_levels : nullptr;
+    d.n_values = c.n_values;
+    d.type = c.physical_type;
+    d.max_def = c.max_def;
+    d.column = col;
+    d.null_idx = -1;
+    if (d.dl) {
+      d.null_idx = (int32_t)fc->n_nullable;
+      fc->null_slot[fc->n_nullable++] = (uint8_t)s;
+    }
+  }
+  if (any) {
+    // a leaf without a null literal on a dictionary slot: one bit per entry, whole words (a null-literal leaf
+    // depends on validity only)
+    for (size_t i = 0; i < filter->program.size(); i++) {
+      const pqg_filter_node& nd = filter->program[i];
+      if (!is_leaf(nd.op) || (nd.flags & PQG_FILTER_NULL_LITERAL)) continue;
+      const size_t s = (size_t)(std::find(filter->slot_column.begin(), filter->slot_column.end(), nd.column) -
+                                filter->slot_column.begin());
+      if (s >= fc->n_slots || !dt->slot[s].is_dict) continue;
+      const uint64_t words = ((uint64_t)dt->slot[s].n_entries + 63) / 64;
+      dt->leaf_off[i] = dt->table_words;
+      dt->table_words += words;
+      if (words) dt->table_leaf[dt->n_tables++] = (uint8_t)i;
+      if (words > dt->max_words) dt->max_words = words;
+    }
+    dt->in_lds = dt->table_words && dt->table_words * 8 <= PQG_FILTER_DICT_LDS_BYTES;
+  }
+  if (any_dict) *any_dict = any;
+  return PQG_OK;
+}
+
+}  // namespace pqg

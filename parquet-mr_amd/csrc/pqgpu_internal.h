@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/pqgpu.h"
+#include "pqgpu_filter.h"
 
 namespace pqg {
 
@@ -245,31 +246,19 @@ struct AsmParams {
 };
 hipError_t launch_assemble(hipStream_t st, const uint8_t* def, const uint8_t* rep, uint64_t n, const AsmParams& P,
                            uint64_t* block_counts, uint32_t n_blocks, uint64_t* totals, uint32_t* ticket, int phase);
-// pqgpu_filter.hip: pqg_filter_run. The columns the program reads (its slots), passed to the kernels
-// by value; null_slot lists the slots that have definition levels (the columns k_filter_rank counts).
-struct FilterColDev {
-  const void* values;
-  const uint8_t* binary;
-  const uint8_t* dl;     // null: required (max_def == 0) or missing (max_def > 0)
-  uint64_t n_values;
-  int32_t type;
-  int32_t max_def;
-  int32_t column;        // the caller's column index (error_column)
-  int32_t null_idx;      // position in null_slot, -1 without definition levels
-};
-struct FilterCols {
-  uint32_t n_slots, n_nullable;
-  uint8_t null_slot[PQG_FILTER_MAX_NODES];
-  FilterColDev c[PQG_FILTER_MAX_NODES];
-};
-// scratch (u64 words): rank[n_nullable][n_tiles], sel[n_tiles], totals[PQG_FILTER_MAX_NODES], bad[PQG_FILTER_MAX_NODES]
+// pqgpu_filter.hip: pqg_filter_run / pqg_filter_run_dict (FilterCols, FilterDictTab: pqgpu_filter.h).
+// scratch (u64 words): rank[n_nullable][n_tiles], sel[n_tiles], totals[PQG_FILTER_MAX_NODES], bad[PQG_FILTER_MAX_NODES],
+// and with dictionaries dict_bad[PQG_FILTER_MAX_NODES] (a slot's bad-id flag), tables[table_words] (the leaves'
+// verdict tables, one bit per dictionary entry)
 inline uint64_t filter_tiles(uint64_t n_rows) { return (n_rows + PQG_FILTER_TILE_ROWS - 1) / PQG_FILTER_TILE_ROWS; }
-inline uint64_t filter_scratch_words(uint64_t n_rows, uint32_t n_nullable) {
-  return ((uint64_t)n_nullable + 1) * filter_tiles(n_rows) + 2 * PQG_FILTER_MAX_NODES;
+inline uint64_t filter_scratch_words(uint64_t n_rows, uint32_t n_nullable, uint64_t dict_words = 0) {
+  return ((uint64_t)n_nullable + 1) * filter_tiles(n_rows) + 2 * PQG_FILTER_MAX_NODES + dict_words;
 }
+// d_dict: the FilterDictTab on the device (null: no dictionary columns), h_dict: the same on the host
 hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_bytes, const FilterCols& cols,
                          uint64_t n_rows, uint64_t* scratch, uint64_t* bitmap, int64_t* row_ids, uint64_t row_ids_capacity,
-                         pqg_filter_result* result);
+                         pqg_filter_result* result, const FilterDictTab* d_dict = nullptr,
+                         const FilterDictTab* h_dict = nullptr);
 // pqgpu_take.hip: pqg_take. scratch (u64 words): keep[n_tiles], rank[n_cols][n_tiles], kept[n_cols][n_tiles],
 // bytes[n_cols][n_tiles] (per-tile counts, scanned in place), totals[1 + 3 n_cols]
 struct TakeColDev;

@@ -257,6 +257,17 @@ class FilterResult(C.Structure):
 
 assert C.sizeof(FilterNode) == 32 and C.sizeof(FilterColumn) == 40 and C.sizeof(FilterResult) == 16
 
+# record filter on dictionary ids (pqg_filter_run_dict)
+FILTER_DICT_LDS_BYTES = 8192  # PQG_FILTER_DICT_LDS_BYTES: verdict tables up to this many bytes are staged in LDS
+
+
+class FilterDictionary(C.Structure):
+    """pqg_filter_dictionary (24 bytes): the decoded dictionary of an id column; values NULL = a value column."""
+    _fields_ = [("values", C.c_void_p), ("binary_data", C.c_void_p), ("n_entries", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(FilterDictionary) == 24
+
 
 # ---- row selection (include/pqgpu.h, "row selection") -----------------------------------------------
 TAKE_MAX_COLUMNS = 64  # PQG_TAKE_MAX_COLUMNS: columns per pqg_take call

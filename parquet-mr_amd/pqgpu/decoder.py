@@ -44,6 +44,7 @@ class DeviceColumn:
         self.n_values = 0
         self.max_def = 0 if def_levels is None else 1  # alloc_columns sets the column's own
         self.flags = 0                                 # pqg_column_desc.flags (COLUMN_DICTIONARY_IDS)
+        self.dictionary = None  # an id column's decoded dictionary (Decoder.decode_dictionary), set by the caller
 
     def offsets(self):
         """BYTE_ARRAY: int64 offsets[n_values + 1] (device tensor)."""
@@ -386,6 +387,46 @@ class Decoder:
             native.check(rc, st, "pqg_decode")
         return cols, st
 
+    def decode_dictionary(self, dbatch, column_index):
+        """The dictionary page of column `column_index` of `dbatch` as a required DeviceColumn of
+        dict_num_values values (pqg_decode_dictionary): what an id column (COLUMN_DICTIONARY_IDS) takes as
+        its `.dictionary` for Decoder.filter. A BYTE_ARRAY byte buffer that turns out short is grown and the
+        page decoded again, as in decode()."""
+        cd = dbatch.batch.columns[column_index]
+        t, tl, n = cd["physical_type"], cd["type_length"], int(cd["dict_num_values"])
+        w = abi.elem_width(t, tl)
+        binary = None
+        if t == abi.BYTE_ARRAY:
+            vals = torch.empty(max((n + 1) * 8, 16), dtype=torch.uint8, device=self.device)
+            binary = torch.empty(int(cd["dict_size"]) + 64, dtype=torch.uint8, device=self.device)
+        else:
+            vals = torch.empty(max(n * w, 16), dtype=torch.uint8, device=self.device)
+        if self.poison is not None:
+            vals.fill_(self.poison)
+        col = DeviceColumn(t, vals, None, None, tl, binary)
+        L = native.lib()
+        for _ in range(2):
+            desc = abi.ColumnDesc()
+            for k, v in cd.items():
+                setattr(desc, k, v)
+            desc.flags = 0
+            desc.values = col.values.data_ptr()
+            desc.values_capacity = n + (1 if t == abi.BYTE_ARRAY else 0)
+            if binary is not None:
+                desc.binary_data = col.binary_data.data_ptr()
+                desc.binary_capacity = col.binary_data.numel()
+            st = abi.Status()
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            rc = L.pqg_decode_dictionary(self.ctx, dbatch.bytes.data_ptr(), dbatch.n_bytes, C.byref(desc), C.byref(st))
+            if rc == abi.OK:
+                rc = L.pqg_sync(self.ctx, C.byref(st))
+            if not (rc == abi.ERR_INVALID_ARG and st.page == -1 and st.message.startswith(b"binary capacity")):
+                break
+            col.binary_data = torch.empty(int(st.value_index) + 64, dtype=torch.uint8, device=self.device)
+        native.check(rc, st, "pqg_decode_dictionary")
+        col.n_values = int(desc.values_written)
+        return col
+
     def _decode_once(self, dbatch, cols, page_counts):
         batch = dbatch.batch
         self.stream.wait_stream(torch.cuda.current_stream(self.device))  # uploads / allocations first
@@ -560,22 +601,34 @@ class Decoder:
             ids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self.device) if row_ids else None
             result = torch.empty(16, dtype=torch.uint8, device=self.device)
         arr = (abi.FilterColumn * max(1, len(cols)))()
+        dicts = None  # pqg_filter_dictionary per column, once a column carries its dictionary
         for i, c in enumerate(cols):
             if getattr(c, "max_rep", 0) or getattr(c, "rep_levels", None) is not None:
                 raise native.PqgError(abi.ERR_UNSUPPORTED, what="filter on a repeated column")
-            arr[i].physical_type = c.physical_type
+            d = getattr(c, "dictionary", None) if getattr(c, "flags", 0) & abi.COLUMN_DICTIONARY_IDS else None
+            if d is not None:
+                if dicts is None:
+                    dicts = (abi.FilterDictionary * len(cols))()
+                dicts[i].values = d.values.data_ptr()
+                dicts[i].binary_data = d.binary_data.data_ptr() if d.binary_data is not None else None
+                dicts[i].n_entries = d.n_values
+            arr[i].physical_type = c.physical_type if d is None else d.physical_type
             arr[i].max_def = c.max_def
             arr[i].values = c.values.data_ptr() if c.values is not None else None
             arr[i].binary_data = c.binary_data.data_ptr() if c.binary_data is not None else None
             arr[i].def_levels = c.def_levels.data_ptr() if c.def_levels is not None else None
             arr[i].n_values = c.n_values
         self.stream.wait_stream(torch.cuda.current_stream(self.device))  # allocations / fills first
-        rc = native.lib().pqg_filter_run(self.ctx, flt.handle, C.addressof(arr), len(cols), n_rows, words.data_ptr(),
-                                         ids.data_ptr() if ids is not None else None, capacity if ids is not None else 0,
-                                         result.data_ptr())
+        outs = (words.data_ptr(), ids.data_ptr() if ids is not None else None, capacity if ids is not None else 0,
+                result.data_ptr())
+        if dicts is None:
+            rc = native.lib().pqg_filter_run(self.ctx, flt.handle, C.addressof(arr), len(cols), n_rows, *outs)
+        else:
+            rc = native.lib().pqg_filter_run_dict(self.ctx, flt.handle, C.addressof(arr), C.addressof(dicts), len(cols),
+                                                  n_rows, *outs)
         native.check(rc, what="pqg_filter_run")
         sel = F.Selection(self, n_rows, words[:n_words], ids, result, capacity)
-        sel._keep = (flt, cols)
+        sel._keep = (flt, cols, [getattr(c, "dictionary", None) for c in cols])
         return sel
 
     # -- row selection ----------------------------------------------------------------

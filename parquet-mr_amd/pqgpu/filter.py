@@ -96,12 +96,18 @@ class Compiled:
 
 
 def column_types(columns):
-    """Physical types of `columns`: ints, or objects with .physical_type (DeviceColumn, MissingColumn)."""
+    """Physical types of `columns`: ints, or objects with .physical_type (DeviceColumn, MissingColumn).
+    A column decoded as dictionary ids counts with its dictionary's type when it carries the decoded
+    dictionary (DeviceColumn.dictionary, from Decoder.decode_dictionary); without one it is refused."""
     out = []
     for c in columns:
         if getattr(c, "flags", 0) & abi.COLUMN_DICTIONARY_IDS:
-            raise native.PqgError(abi.ERR_UNSUPPORTED, what="filter on a column decoded as dictionary ids")
-        out.append(int(getattr(c, "physical_type", c)))
+            d = getattr(c, "dictionary", None)
+            if d is None:
+                raise native.PqgError(abi.ERR_UNSUPPORTED, what="filter on a column decoded as dictionary ids")
+            out.append(int(d.physical_type))
+        else:
+            out.append(int(getattr(c, "physical_type", c)))
     return out
 
 
@@ -221,7 +227,9 @@ class Selection:
             n = int(r[:8].view(np.uint64)[0])
             err, err_col = (int(x) for x in r[8:16].view(np.int32))
             if err != abi.OK:
-                raise native.PqgError(err, what=f"pqg_filter_run: column {err_col}: rows with a value differ from n_values")
+                why = ("a dictionary id outside the dictionary" if err == abi.ERR_DICT_ID else
+                       "rows with a value differ from n_values")
+                raise native.PqgError(err, what=f"pqg_filter_run: column {err_col}: {why}")
             self._host = n
         return self._host
 

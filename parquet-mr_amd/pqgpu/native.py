@@ -32,6 +32,8 @@ EXPORTS = [
     "pqg_lr_skip", "pqg_java_exception",
     # record filter (filter2 predicates over decoded columns)
     "pqg_filter_create", "pqg_filter_program", "pqg_filter_destroy", "pqg_filter_run",
+    # ... on dictionary-id columns, and the dictionary itself as a column
+    "pqg_filter_run_dict", "pqg_decode_dictionary",
     # row selection (the rows a bitmap keeps, as compact columns)
     "pqg_take",
 ]
@@ -106,6 +108,8 @@ def lib():
         L.pqg_filter_program.argtypes = [vp, vp, i32]
         L.pqg_filter_destroy.argtypes = [vp]
         L.pqg_filter_run.argtypes = [vp, vp, vp, i32, u64, vp, vp, u64, vp]
+        L.pqg_filter_run_dict.argtypes = [vp, vp, vp, vp, i32, u64, vp, vp, u64, vp]
+        L.pqg_decode_dictionary.argtypes = [vp, vp, u64, vp, C.POINTER(abi.Status)]
         L.pqg_take.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
         L.pqg_error_name.argtypes = [i32]
         L.pqg_error_name.restype = C.c_char_p
