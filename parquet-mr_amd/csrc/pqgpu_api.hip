@@ -16,6 +16,7 @@
 #include <new>
 #include <atomic>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "pqgpu_internal.h"
@@ -24,6 +25,14 @@
 
 using pqg::ColumnDev;
 using pqg::PageWork;
+using pqg::HostErr;
+using pqg::bin_out;
+using pqg::elem_width;
+using pqg::out_width;
+// pqg::Cls
+using pqg::C_DICT4; using pqg::C_DICT8; using pqg::C_IDS; using pqg::C_PLAIN; using pqg::C_BOOL; using pqg::C_DELTA4;
+using pqg::C_DELTA8; using pqg::C_BSS; using pqg::C_BINP; using pqg::C_DLBA; using pqg::C_DBA; using pqg::C_RLEBOOL;
+using pqg::C_DD; using pqg::C_DDG; using pqg::C_NCLS;
 
 namespace {
 
@@ -76,45 +85,39 @@ struct PinnedBuf {
   }
 };
 
-int elem_width(int t, int tl) {
-  switch (t) {
-    case PQG_BOOLEAN: return 1;
-    case PQG_INT32: case PQG_FLOAT: return 4;
-    case PQG_INT64: case PQG_DOUBLE: return 8;
-    case PQG_INT96: return 12;
-    case PQG_FIXED_LEN_BYTE_ARRAY: return tl;
-    default: return 0;
-  }
-}
-
-// PQG_COLUMN_DICTIONARY_IDS columns write uint32 ids; BYTE_ARRAY columns otherwise write offsets + bytes
-bool ids_mode(const pqg_column_desc& c) { return (c.flags & PQG_COLUMN_DICTIONARY_IDS) != 0; }
-bool bin_out(const pqg_column_desc& c) { return c.physical_type == PQG_BYTE_ARRAY && !ids_mode(c); }
-int out_width(const pqg_column_desc& c) { return ids_mode(c) ? 4 : elem_width(c.physical_type, c.type_length); }
-
 // Error words: 3 per page + 3 per column (dictionary pages), padded to 16 bytes; the error
 // counter follows them in the same allocation.
 size_t err_region_bytes(int n_pages, int n_cols) {
   return (sizeof(uint64_t) * 3 * (size_t)(n_pages + std::max(n_cols, 1)) + 15) & ~(size_t)15;
 }
 
-// Kernel classes, in launch order after the level pass.
-//   C_IDS   dictionary pages whose values are not 4 / 8 bytes (BYTE_ARRAY, FLBA, INT96): ids first
-//   C_BINP  PLAIN BYTE_ARRAY          C_DLBA  DELTA_LENGTH_BYTE_ARRAY      C_BSS  BYTE_STREAM_SPLIT
-//   C_DBA   DELTA_BYTE_ARRAY (lengths here; values by k_dba_copy after the offset scan)
-//   C_DD    dictionary pages of dictionary-direct BYTE_ARRAY columns (ColumnDev::dict_direct): walk + chunk
-//           byte sums, per-column scan, offsets + value bytes (launch_dict_dd), no ids stored
-//   C_DDG   the same for dictionary-direct columns whose dictionary is gathered from HBM (ColumnDev::dd_global)
-enum Cls { C_DICT4 = 0, C_DICT8, C_IDS, C_PLAIN, C_BOOL, C_DELTA4, C_DELTA8, C_BSS, C_BINP, C_DLBA, C_DBA, C_RLEBOOL, C_DD,
-           C_DDG, C_NCLS };
-constexpr int N_DICT_CLS = 3;  // C_DICT4, C_DICT8, C_IDS: run-record walk + chunk expansion
-
-struct HostErr {
-  int page;
-  int kind;  // 0 init, 2 value
-  int64_t index;
-  int code;
+// The device buffers of a plan.
+enum PlanBuf {
+  B_WORK, B_COLS, B_LISTS, B_COL_PAGES, B_COL_PAGE_START, B_ERR,
+  // BYTE_ARRAY / fixed-width-dictionary scratch (PlanLayout::regions), dictionary walks, post-passes,
+  // offset-scan blocks, copy chunks
+  B_BSCRATCH, B_BIN_LISTS, B_BIN_BLOCKS, B_BIN_CHUNKS, B_DBA_CHUNKS,
+  B_SEGS,        // PLAIN BYTE_ARRAY segments (k_bin_walk_seg)
+  B_DENT_TILES,  // large dictionaries' tiles (launch_dict_entries)
+  B_PSEGS, B_PSTATUS, B_PCOL_PAGES, B_PCOL_START,  // one-pass PLAIN: tiles; aggw + incw per tile; column page lists
+  B_REC, B_CHUNK_RUN, B_CHUNKS,  // dictionary pages: run records, chunk -> record, chunk work list
+  B_PSTAT, B_FLAGS,              // per page: {records, values} and ready epoch (fused dictionary kernel)
+  B_COUNT
 };
+
+// One row per buffer: what plan creation allocates (`alloc` bytes, with the slack the kernels read past
+// the tables' ends) and how it fills the first `bytes`: copied from `host`, or zeroed.
+struct PlanBufInit {
+  PlanBuf buf;
+  const void* host;
+  size_t bytes, alloc;
+  bool zero;
+};
+
+template <class T>
+PlanBufInit uploaded(PlanBuf b, const std::vector<T>& v, size_t min_elems) {
+  return PlanBufInit{b, v.data(), sizeof(T) * v.size(), sizeof(T) * std::max(v.size(), min_elems), false};
+}
 
 }  // namespace
 
@@ -122,83 +125,30 @@ struct pqg_plan {
   pqg_ctx* ctx = nullptr;
   const uint8_t* d_bytes = nullptr;
   uint64_t n_bytes = 0;
-  int n_pages = 0;
-  int n_cols = 0;
-  DevBuf work, cols, lists, col_pages, col_page_start, err;
-  DevBuf rec, chunk_run, chunks;      // dictionary pages: run records, chunk -> record, chunk work list
-  DevBuf pstat, flags;                // per page: {records, values} and ready epoch (fused dictionary kernel)
+  pqg::PlanLayout L;  // what the planner computed from the descriptors (pqgpu_plan.h)
+  DevBuf buf[B_COUNT];
+  uint32_t* dba_meta() const {
+    return L.dba_meta_off == pqg::NO_REGION ? nullptr : (uint32_t*)((uint8_t*)buf[B_BSCRATCH].p + L.dba_meta_off);
+  }
+  // ---- launch-time state
   uint32_t epoch = 0;
   uint32_t err_epoch = pqg::ERR_EPOCH_MAX;  // error-word epoch of the last launch (first launch wraps: zeroes the region)
+  uint32_t pseg_epoch = 0;                  // k_bin_plain tile words' epoch (1..255)
   bool dict_fused = true;
-  uint32_t chunk_off[N_DICT_CLS] = {0, 0, 0}, chunk_n[N_DICT_CLS] = {0, 0, 0};  // ranges in `chunks`
-  // C_DD: its chunks in `chunks` (per column in page order, each column's first at a multiple of 4:
-  // padding entries of page 0xFFFFFFFF between columns), the per-chunk byte sums / first bytes in
-  // bscratch, the columns and their chunk ranges in bin_lists, the LDS of the staged dictionaries
-  // ([0]: C_DD, dictionaries staged in LDS; [1]: C_DDG, dictionaries gathered from HBM)
-  uint32_t dd_chunk_off[2] = {0, 0}, dd_chunk_n[2] = {0, 0}, dd_region = 16;
-  uint64_t dd_sums_off[2] = {~0ull, ~0ull};
-  int n_dd_cols[2] = {0, 0}, off_dd_cols[2] = {0, 0}, off_dd_start[2] = {0, 0};
-  // fused dictionary kernel: persistent walker / tile workgroup counts (0: one page / 4 chunks per WG)
-  // BYTE_ARRAY / fixed-width-dictionary scratch (ColumnDev::blen, bsrc, dict_len, dict_src, block_sums,
-  // bin_total), dictionary walks, post-passes, offset-scan blocks, copy chunks
-  DevBuf bscratch, bin_lists, bin_blocks, bin_chunks, dba_chunks;
-  uint64_t blen_bytes = 0;            // leading part of bscratch cleared before every launch
-  int n_dict_walk = 0, n_bind = 0, n_fixd = 0, n_bin_cols = 0, n_carry = 0;
-  // BYTE_ARRAY dictionary pages of at least DENT_MIN bytes: walked per tile (launch_dict_entries)
-  DevBuf dent_tiles;
-  uint32_t n_dent_tiles = 0;
-  int n_dent_cols = 0, off_dent_cols = 0, off_dent_start = 0;
-  uint64_t dent_rec_off = 0, dent_scr_off = 0, dent_tb_off = 0;
-  int off_dict_walk = 0, off_bind = 0, off_fixd = 0, off_bin_cols = 0, off_carry = 0;  // into bin_lists
-  uint32_t n_bin_blocks = 0, n_bin_chunks = 0, n_dba_chunks = 0;
-  uint64_t dba_meta_off = ~0ull;  // DELTA_BYTE_ARRAY per-chunk {suffix base, smallest prefix} in bscratch
-  uint32_t* dba_meta() const {
-    return dba_meta_off == ~0ull ? nullptr : (uint32_t*)((uint8_t*)bscratch.p + dba_meta_off);
-  }
-  std::vector<uint64_t> bin_total_off;  // per column: byte offset of its bin_total in bscratch (or ~0)
-  std::vector<uint64_t> bin_capacity;
-  std::vector<int> col_first_page;
-  std::vector<void*> empty_bin_values; // BYTE_ARRAY columns without slots: offsets[0] = 0
-  std::vector<PageWork> h_work;
-  std::vector<int> cls_off, cls_n;  // into lists
-  int levels_off = 0, levels_n = 0;
-  int n_scan_cols = 0;
-  std::vector<int> page_cls;        // -1 if not launched
-  std::vector<uint8_t> col_nullable;
-  std::vector<uint64_t> col_required_values;
-  std::vector<HostErr> host_errs;
-  std::vector<pqg_page_error> page_errs;  // per page, resolved by pqg_sync (pqg_page_errors)
-  int kernels = 0;
-  DevBuf segs;                        // PLAIN BYTE_ARRAY segments (k_bin_walk_seg): page | s << 32 | last << 63
-  uint32_t n_segs = 0;
-  uint64_t seg_status_off = 0, seg_tmp_off = 0;  // in bscratch: status words + ticket (cleared per launch), scratch
-  int timeout_fallbacks = 0;           // launches re-run in split mode after PQG_ERR_TIMEOUT (pqg_sync)
-  // PLAIN-only BYTE_ARRAY columns in one pass (k_bin_bases + k_bin_plain); the per-value path's lists
-  // hold those columns' entries last, so plain_fused launches skip them (pqg_sync turns plain_fused
-  // off when a page's values do not fill its data section)
+  // one-pass PLAIN columns (pqg_sync turns plain_fused off when a page's values do not fill its data section)
   bool plain_fused = false;
-  bool plain_pg = false;  // ... through k_bin_plain_pg (one wave per page) instead of the tiles
-  int n_pcp = 0;          // pages of those columns (pcol_pages)
-  int plain_fallbacks = 0;
-  DevBuf psegs, pstatus, pcol_pages, pcol_start;  // tiles (page | tile << 32); aggw + incw per tile; column page lists
-  uint32_t n_psegs = 0, pseg_epoch = 0;
-  int n_pcols = 0;
-  uint64_t pticket_off = 0, pflag_off = 0;  // in bscratch: ticket (cleared per launch), inexact flag (epoch-tagged)
-  uint64_t blen_bytes_nf = 0;               // cleared part of bscratch when plain_fused
-  int n_binp_fused = 0, n_bin_cols_nf = 0;  // tails of cls_lists[C_BINP] / bin_cols that belong to those columns
-  // pages k_bin_walk_seg walks (the last n_binp_seg of cls_lists[C_BINP], after the one-pass columns'
-  // pages); seg_walk false: one wave per page instead (pqg_sync's re-run after a segment wait timed out)
-  int n_binp_seg = 0;
+  // seg_walk false: the segmented PLAIN pages one wave per page instead (pqg_sync's re-run after a segment
+  // wait timed out)
   bool seg_walk = true;
-  uint32_t n_bin_blocks_nf = 0, n_bin_chunks_nf = 0;
-  // V2 header null counts (PQG_PAGE_NULL_COUNT): every nullable page of the plan carries one, so the
-  // host filled those pages' n_values / data_begin / out_offset and the value kernels start beside
-  // k_levels, which verifies the counts into the epoch-tagged word at hint_off (bscratch); a mismatch
-  // makes pqg_sync re-run level-first, and the plan keeps that order (null_hints false)
+  // V2 header null counts in use; a mismatch makes pqg_sync re-run level-first, and the plan keeps that
+  // order (null_hints false)
   bool null_hints = false;
-  uint64_t hint_off = 0;
+  int kernels = 0;
+  int timeout_fallbacks = 0;  // launches re-run in split mode after PQG_ERR_TIMEOUT (pqg_sync)
+  int plain_fallbacks = 0;
   int hint_fallbacks = 0;
   uint32_t* d_counts = nullptr;  // pqg_decode's d_page_value_counts (refreshed after a re-run)
+  std::vector<pqg_page_error> page_errs;  // per page, resolved by pqg_sync (pqg_page_errors)
 };
 
 // pqg_router_read_page: the bit-packed runs of a hybrid stream's tail, walked on the host at the first
@@ -432,20 +382,8 @@ int pqg_ctx_destroy(pqg_ctx* c) {
 // valid_bytes: the caller's data ends there (page and dictionary extents are checked against it); the
 // kernels may read up to n_bytes (pqg_decode_host's zero padding past the caller's bytes)
 // Kernels one launch of the plan runs (in its current modes).
-static int count_kernels(const pqg_plan* P) {
-  const bool pf = P->plain_fused;
-  int k = (P->levels_n ? 1 : 0) + (P->n_scan_cols && !P->null_hints ? 1 : 0);
-  for (int c = 0; c < C_NCLS; c++) {
-    const int n = P->cls_n[(size_t)c] - (c == C_BINP ? P->n_binp_seg + (pf ? P->n_binp_fused : 0) : 0);
-    if (n && c == C_DD) k += P->dict_fused ? 3 : 4;
-    else if (n && c == C_DDG) k += P->dict_fused ? 4 : 5;
-    else if (n) k += (c == C_DICT4 || c == C_DICT8 || c == C_IDS) && !P->dict_fused ? 2 : 1;
-  }
-  k += (P->n_dict_walk ? 1 : 0) + (P->n_dent_tiles ? 3 : 0) + (P->n_bind ? 1 : 0) + (P->n_fixd ? 1 : 0) +
-       ((pf ? P->n_bin_blocks_nf : P->n_bin_blocks) ? 3 : 0) + ((pf ? P->n_bin_chunks_nf : P->n_bin_chunks) ? 1 : 0) +
-       (P->cls_n[C_DBA] ? (P->n_dba_chunks ? 4 : 1) : 0) + (P->n_carry ? 1 : 0) + (P->n_segs ? 1 : 0) +
-       (pf ? 2 : 0);
-  return k;
+static int plan_kernels(const pqg_plan* P) {
+  return pqg::plan_kernel_count(P->L, P->plain_fused, P->dict_fused, P->null_hints);
 }
 
 static int plan_create_impl(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, uint64_t valid_bytes,
@@ -461,609 +399,82 @@ static int plan_create_impl(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_byt
   pqg_plan* P = new (std::nothrow) pqg_plan();
   if (!P) return PQG_ERR_INVALID_ARG;
   P->ctx = ctx;
-  P->dict_fused = ctx->dict_fused;
   P->d_bytes = d_bytes;
   P->n_bytes = n_bytes;
-  P->n_pages = n_pages;
-  P->n_cols = n_cols;
-  // ---- columns
-  std::vector<ColumnDev> hc((size_t)std::max(n_cols, 1));
-  std::vector<int> col_err((size_t)std::max(n_cols, 1), 0);
-  std::vector<int> col_first_page((size_t)std::max(n_cols, 1), -1);
-  P->col_nullable.assign((size_t)std::max(n_cols, 1), 0);
-  P->col_required_values.assign((size_t)std::max(n_cols, 1), 0);
-  for (int i = 0; i < n_cols; i++) {
-    const pqg_column_desc& c = cols[i];
-    ColumnDev& d = hc[(size_t)i];
-    std::memset(&d, 0, sizeof(d));
-    d.physical_type = c.physical_type;
-    d.type_length = c.type_length;
-    d.max_rep = c.max_rep;
-    d.max_def = c.max_def;
-    d.elem_width = elem_width(c.physical_type, c.type_length);
-    d.values = c.values;
-    d.binary_data = c.binary_data;
-    d.binary_capacity = bin_out(c) ? c.binary_capacity : 0;
-    d.def_levels = c.max_def > 0 ? c.def_levels : nullptr;
-    d.rep_levels = c.max_rep > 0 ? c.rep_levels : nullptr;
-    P->col_nullable[(size_t)i] = (c.max_def > 0 || c.max_rep > 0) ? 1 : 0;
-    if (c.max_def > 254 || c.max_rep > 254 || c.max_def < 0 || c.max_rep < 0) col_err[(size_t)i] = PQG_ERR_UNSUPPORTED;
-    if (c.dict_offset >= 0) {
-      // PlainValuesDictionary ctor :47-53 and the typed readers: validated from the descriptor
-      if (c.dict_encoding != PQG_PLAIN && c.dict_encoding != PQG_PLAIN_DICTIONARY) {
-        col_err[(size_t)i] = PQG_ERR_DICT_ENCODING;
-      } else if (c.physical_type == PQG_BOOLEAN) {
-        col_err[(size_t)i] = PQG_ERR_UNSUPPORTED;
-      } else if (c.physical_type == PQG_FIXED_LEN_BYTE_ARRAY && c.type_length <= 0) {
-        col_err[(size_t)i] = PQG_ERR_CORRUPT;  // PlainBinaryDictionary :106 checkArgument(length > 0)
-      } else if ((uint64_t)c.dict_offset + c.dict_size > valid_bytes) {
-        col_err[(size_t)i] = PQG_ERR_INVALID_ARG;
-      } else if (d.elem_width > 0 && (uint64_t)c.dict_num_values * (uint64_t)d.elem_width > c.dict_size) {
-        col_err[(size_t)i] = PQG_ERR_EOF;
-      }
-      d.dict_n = c.dict_num_values;
-      d.dict_offset = (uint64_t)c.dict_offset;
-      d.dict_bytes = c.dict_size;
-    }
+  pqg::PlanLayout& L = P->L;
+  int bad_page = -1;
+  if (pqg::plan_layout(n_bytes, valid_bytes, cols, n_cols, pages, n_pages,
+                       pqg::PlanOptions{ctx->plain_mode, ctx->dict_direct, ctx->null_hints}, &L, &bad_page) != PQG_OK) {
+    set_status(st, PQG_ERR_INVALID_ARG, bad_page, -1, "page descriptor");
+    delete P;
+    return PQG_ERR_INVALID_ARG;
   }
-  // ---- pages
-  P->h_work.resize((size_t)std::max(n_pages, 1));
-  P->page_cls.assign((size_t)std::max(n_pages, 1), -1);
-  std::vector<std::vector<int>> cls_lists(C_NCLS);
-  std::vector<int> lvl_list;
-  std::vector<std::vector<int>> col_pages((size_t)std::max(n_cols, 1));
-  std::vector<uint64_t> slot_acc((size_t)std::max(n_cols, 1), 0), val_acc((size_t)std::max(n_cols, 1), 0);
-  // per column: class of its previous page (-2: none yet; PQG_PAGE_DBA_CARRY needs a DELTA_BYTE_ARRAY
-  // one), FIXED_LEN_BYTE_ARRAY with DELTA_BYTE_ARRAY pages, any carry page
-  std::vector<int> col_last_cls((size_t)std::max(n_cols, 1), -2);
-  std::vector<uint8_t> dba_fixed((size_t)std::max(n_cols, 1), 0), dba_carry((size_t)std::max(n_cols, 1), 0);
-  for (int p = 0; p < n_pages; p++) {
-    const pqg_page_desc& g = pages[p];
-    PageWork& w = P->h_work[(size_t)p];
-    std::memset(&w, 0, sizeof(w));
-    if (g.column < 0 || g.column >= n_cols || g.offset + g.size > valid_bytes || g.offset + g.size < g.offset || (g.version != 1 && g.version != 2)) {
-      set_status(st, PQG_ERR_INVALID_ARG, p, -1, "page descriptor");
-      delete P;
-      return PQG_ERR_INVALID_ARG;
-    }
-    const int ci = g.column;
-    const pqg_column_desc& c = cols[ci];
-    if (col_first_page[(size_t)ci] < 0) {
-      col_first_page[(size_t)ci] = p;
-      if (col_err[(size_t)ci]) P->host_errs.push_back(HostErr{p, 0, -1, col_err[(size_t)ci]});
-    }
-    w.base = g.offset;
-    w.size = g.size;
-    w.num_slots = g.num_values;
-    w.column = ci;
-    w.version = g.version;
-    w.rl_encoding = g.rl_encoding;
-    w.dl_encoding = g.dl_encoding;
-    w.rl_len = g.rl_byte_length;
-    w.dl_len = g.dl_byte_length;
-    w.pflags = g.flags;
-    w.slot_offset = slot_acc[(size_t)ci];
-    slot_acc[(size_t)ci] += g.num_values;
-    const bool nullable = P->col_nullable[(size_t)ci] != 0;
-    if (!nullable) {
-      // required column: no level sections are consumed (ZeroIntegerValuesReader / BIT_PACKED
-      // width 0 / NullIntIterator), values = header num_values
-      if (g.version == 1 && ((g.rl_encoding != PQG_RLE && g.rl_encoding != PQG_BIT_PACKED) ||
-                             (g.dl_encoding != PQG_RLE && g.dl_encoding != PQG_BIT_PACKED))) {
-        P->host_errs.push_back(HostErr{p, 0, 0, PQG_ERR_UNSUPPORTED});
-        continue;
-      }
-      uint64_t lv = g.version == 2 ? (uint64_t)g.rl_byte_length + g.dl_byte_length : 0;
-      if (lv > g.size) {
-        P->host_errs.push_back(HostErr{p, 0, 0, PQG_ERR_CORRUPT});
-        continue;
-      }
-      w.data_begin = (uint32_t)lv;
-      w.n_values = g.num_values;
-      w.out_offset = val_acc[(size_t)ci];
-      val_acc[(size_t)ci] += g.num_values;
-    } else {
-      lvl_list.push_back(p);
-      col_pages[(size_t)ci].push_back(p);
-    }
-    const int last_cls = col_last_cls[(size_t)ci];
-    col_last_cls[(size_t)ci] = -1;
-    if (col_err[(size_t)ci]) continue;  // dictionary page unusable: ColumnReaderBase ctor threw
-    // value class (Encoding.getValuesReader / getDictionaryBasedValuesReader dispatch)
-    const int t = c.physical_type;
-    const int ew = elem_width(t, c.type_length);
-    int cls = -1, herr = 0;
-    if (ids_mode(c)) {
-      // readValueDictionaryId: dictionary pages give their ids (any physical type, k_dict_fused<4, IDS>
-      // writing straight into the column's uint32 values); other readers throw (ValuesReader.java:123-125)
-      if (g.encoding != PQG_PLAIN_DICTIONARY && g.encoding != PQG_RLE_DICTIONARY) herr = PQG_ERR_UNSUPPORTED;
-      else if (c.dict_offset < 0) herr = PQG_ERR_NO_DICTIONARY;
-      else if (t == PQG_BOOLEAN) herr = PQG_ERR_UNSUPPORTED;
-      else cls = C_IDS;
-    } else
-    switch (g.encoding) {
-      case PQG_PLAIN_DICTIONARY:
-      case PQG_RLE_DICTIONARY:
-        if (c.dict_offset < 0) herr = PQG_ERR_NO_DICTIONARY;
-        else if (t == PQG_BOOLEAN) herr = PQG_ERR_UNSUPPORTED;
-        else if (t == PQG_BYTE_ARRAY) { cls = C_IDS; w.bin_kind = pqg::BIN_DICT; }
-        else if (ew == 8) cls = C_DICT8;
-        else if (ew == 4) cls = C_DICT4;
-        else if (ew > 0) cls = C_IDS;      // FLBA / INT96: ids, then k_gather_fixed
-        else herr = PQG_ERR_UNSUPPORTED;
-        break;
-      case PQG_PLAIN:
-        if (t == PQG_BOOLEAN) cls = C_BOOL;
-        else if (t == PQG_BYTE_ARRAY) { cls = C_BINP; w.bin_kind = pqg::BIN_PLAIN; }
-        else if (ew > 0) cls = C_PLAIN;
-        else herr = PQG_ERR_UNSUPPORTED;
-        break;
-      case PQG_RLE:  // Encoding.RLE values: BOOLEAN only (getMaxLevel :255-271)
-        if (t == PQG_BOOLEAN) cls = C_RLEBOOL;
-        else herr = PQG_ERR_UNSUPPORTED;
-        break;
-      case PQG_DELTA_BINARY_PACKED:
-        if (t == PQG_INT64) cls = C_DELTA8;
-        else if (t == PQG_INT32) cls = C_DELTA4;
-        else herr = PQG_ERR_UNSUPPORTED;
-        break;
-      case PQG_DELTA_LENGTH_BYTE_ARRAY:
-        if (t == PQG_BYTE_ARRAY) { cls = C_DLBA; w.bin_kind = pqg::BIN_DLBA; }
-        else herr = PQG_ERR_UNSUPPORTED;   // Encoding.java :204-207
-        break;
-      case PQG_BYTE_STREAM_SPLIT:
-        if (t == PQG_FLOAT || t == PQG_DOUBLE || t == PQG_INT32 || t == PQG_INT64 ||
-            (t == PQG_FIXED_LEN_BYTE_ARRAY && ew > 0))
-          cls = C_BSS;
-        else
-          herr = PQG_ERR_UNSUPPORTED;      // Encoding.java :130-143
-        break;
-      case PQG_DELTA_BYTE_ARRAY:
-        // Encoding.java :219-222: BYTE_ARRAY and FIXED_LEN_BYTE_ARRAY (whose values must then be
-        // type_length bytes each: k_delta reports any other length as PQG_ERR_CORRUPT)
-        if (t == PQG_BYTE_ARRAY || (t == PQG_FIXED_LEN_BYTE_ARRAY && ew > 0)) {
-          cls = C_DBA;
-          w.bin_kind = pqg::BIN_DBA;
-          if (t == PQG_FIXED_LEN_BYTE_ARRAY) dba_fixed[(size_t)ci] = 1;
-          if (g.flags & PQG_PAGE_DBA_CARRY) {
-            // setPreviousReader casts the previous page's reader to DeltaByteArrayReader
-            if (last_cls != -2 && last_cls != C_DBA) { cls = -1; herr = PQG_ERR_UNSUPPORTED; }
-            else dba_carry[(size_t)ci] = 1;
-          }
-        } else {
-          herr = PQG_ERR_UNSUPPORTED;
-        }
-        break;
-      default:
-        herr = PQG_ERR_UNSUPPORTED;
-    }
-    if (herr) {
-      P->host_errs.push_back(HostErr{p, 0, 2, herr});
-      continue;
-    }
-    P->page_cls[(size_t)p] = cls;
-    col_last_cls[(size_t)ci] = cls;
-    cls_lists[(size_t)cls].push_back(p);
-  }
-  for (int i = 0; i < n_cols; i++) P->col_required_values[(size_t)i] = val_acc[(size_t)i];
-  P->col_first_page = col_first_page;
-  // V2 header null counts as a verified hint (PQG_PAGE_NULL_COUNT): only when every nullable page of the
-  // plan carries a usable one, so that no value kernel has to wait for k_levels
-  if (ctx->null_hints && !lvl_list.empty()) {
-    bool all = true;
-    for (int p : lvl_list) {
-      const pqg_page_desc& g = pages[p];
-      all = all && g.version == 2 && (g.flags & PQG_PAGE_NULL_COUNT) && g.num_nulls <= g.num_values &&
-            (uint64_t)g.rl_byte_length + g.dl_byte_length <= g.size;
-    }
-    if (all) {
-      std::vector<uint64_t> acc((size_t)std::max(n_cols, 1), 0);
-      for (int p : lvl_list) {  // (page order within each column)
-        const pqg_page_desc& g = pages[p];
-        PageWork& w = P->h_work[(size_t)p];
-        w.n_values = g.num_values - g.num_nulls;
-        w.data_begin = g.rl_byte_length + g.dl_byte_length;
-        w.out_offset = acc[(size_t)g.column];
-        acc[(size_t)g.column] += w.n_values;
-      }
-      P->null_hints = true;
-    }
-  }
-  // ---- BYTE_ARRAY and fixed-width dictionary columns: scratch layout, dictionary walks,
-  // post-passes, offset-scan blocks and copy chunks
-  std::vector<int32_t> dict_walk, bind, fixd, bin_cols, carry_cols, dent_cols;
-  std::vector<uint64_t> bin_blocks, bin_chunks;
-  std::vector<uint64_t> blen_off((size_t)std::max(n_cols, 1), ~0ull), bsrc_off = blen_off, dlen_off = blen_off,
-      dsrc_off = blen_off, bsum_off = blen_off, dent_off = blen_off;
-  P->bin_total_off.assign((size_t)std::max(n_cols, 1), ~0ull);
-  P->bin_capacity.assign((size_t)std::max(n_cols, 1), 0);
-  uint64_t sc = 0;
-  auto take = [&](uint64_t bytes) { uint64_t o = sc; sc = (sc + bytes + 255) & ~uint64_t(255); return o; };
-  std::vector<uint8_t> needs_ids((size_t)std::max(n_cols, 1), 0);
-  for (int p : cls_lists[C_IDS]) needs_ids[(size_t)P->h_work[(size_t)p].column] = 1;
-  // PLAIN-only BYTE_ARRAY columns (every page PLAIN, no descriptor error, < 2^24 - 1 slots per page):
-  // one pass: k_bin_bases + k_bin_plain over 2 KiB tiles of their pages when the plan has fewer than
-  // BW_SEG_MAX_PAGES PLAIN pages, k_bin_plain_pg (one wave per page, which fills the chip) with more
-  // (there the tiles measured slower than the per-value walk + copy: C3 10.4 vs 6.4 ms, profiles/r03/plain_ab)
-  // pqg_ctx_set_dispatch(PQG_DISPATCH_PLAIN_ONE_PASS) overrides the choice (tests and A/B): 0 = no
-  // one-pass path (every plan per value), 3 = every plan one wave per page
-  const int plain_mode = ctx->plain_mode;
-  const bool many_plain = (cls_lists[C_BINP].size() >= pqg::BW_SEG_MAX_PAGES && plain_mode != 1) || plain_mode == 3;
-  P->plain_pg = many_plain;
-  std::vector<uint8_t> plain_col((size_t)std::max(n_cols, 1), 0);
-  std::vector<uint64_t> psegs;
-  std::vector<int32_t> pcp, pcs(1, 0);
-  {
-    std::vector<int> npg((size_t)std::max(n_cols, 1), 0), nplain((size_t)std::max(n_cols, 1), 0);
-    std::vector<std::vector<int>> cpg((size_t)std::max(n_cols, 1));
-    for (int p = 0; p < n_pages; p++) {
-      const int c = P->h_work[(size_t)p].column;
-      npg[(size_t)c]++;
-      cpg[(size_t)c].push_back(p);
-      if (P->page_cls[(size_t)p] == C_BINP && P->h_work[(size_t)p].num_slots < (1u << 24) - 1u) nplain[(size_t)c]++;
-    }
-    for (int i = 0; i < n_cols; i++) {
-      plain_col[(size_t)i] = bin_out(cols[i]) && !ids_mode(cols[i]) && !col_err[(size_t)i] && !dba_fixed[(size_t)i] &&
-                             npg[(size_t)i] > 0 && nplain[(size_t)i] == npg[(size_t)i] && plain_mode != 0;
-      if (!plain_col[(size_t)i]) continue;
-      for (int p : cpg[(size_t)i]) {
-        pcp.push_back(p);
-        if (many_plain) continue;
-        const uint32_t ntile = std::max<uint32_t>((P->h_work[(size_t)p].size + pqg::BP_TILE - 1) / pqg::BP_TILE, 1u);
-        for (uint32_t k = 0; k < ntile; k++) psegs.push_back((uint64_t)(uint32_t)p | ((uint64_t)k << 32));
-      }
-      pcs.push_back((int32_t)pcp.size());
-    }
-  }
-  // dictionary-direct BYTE_ARRAY columns (ColumnDev::dict_direct): every data page dictionary-encoded,
-  // the dictionary page small enough to stage (DD_DICT_MAX bytes, at most 2,048 entries): their pages
-  // leave C_IDS for C_DD (no ids stored, no offset scan or copy of their own). Nullable and nested
-  // columns too (round 6): the walk decodes a page's n_values ids from its data section, which k_levels
-  // (or the V2 header counts) give, and values are indexed by out_offset like every other class.
-  // Larger dictionaries (at most 65,536 entries: u16 ids) take C_DDG: their entries and value bytes are
-  // gathered from HBM instead of LDS (k_dd_gsums / k_dd_gstr; round 6)
-  std::vector<uint8_t> dict_direct((size_t)std::max(n_cols, 1), 0), dd_glob((size_t)std::max(n_cols, 1), 0);
-  {
-    std::vector<int> npg((size_t)std::max(n_cols, 1), 0), nids((size_t)std::max(n_cols, 1), 0);
-    for (int p = 0; p < n_pages; p++) {
-      const int c = P->h_work[(size_t)p].column;
-      npg[(size_t)c]++;
-      if (P->page_cls[(size_t)p] == C_IDS) nids[(size_t)c]++;
-    }
-    for (int i = 0; i < n_cols; i++)
-      dict_direct[(size_t)i] = cols[i].physical_type == PQG_BYTE_ARRAY && bin_out(cols[i]) && !ids_mode(cols[i]) &&
-                               !col_err[(size_t)i] && !dba_fixed[(size_t)i] && !plain_col[(size_t)i] &&
-                               cols[i].dict_offset >= 0 && cols[i].dict_num_values <= 65536 &&
-                               npg[(size_t)i] > 0 && nids[(size_t)i] == npg[(size_t)i] && ctx->dict_direct;
-    for (int i = 0; i < n_cols; i++)
-      dd_glob[(size_t)i] = dict_direct[(size_t)i] &&
-                           (cols[i].dict_size > pqg::DD_DICT_MAX || cols[i].dict_num_values > 2048);
-    std::vector<int> keep, dd, ddg;
-    for (int p : cls_lists[C_IDS]) {
-      const int c = P->h_work[(size_t)p].column;
-      (!dict_direct[(size_t)c] ? keep : dd_glob[(size_t)c] ? ddg : dd).push_back(p);
-    }
-    auto by_col = [&](int a, int b) { return P->h_work[(size_t)a].column < P->h_work[(size_t)b].column; };
-    std::stable_sort(dd.begin(), dd.end(), by_col);
-    std::stable_sort(ddg.begin(), ddg.end(), by_col);
-    for (int p : dd) P->page_cls[(size_t)p] = C_DD;
-    for (int p : ddg) P->page_cls[(size_t)p] = C_DDG;
-    cls_lists[C_IDS].swap(keep);
-    cls_lists[C_DD].swap(dd);
-    cls_lists[C_DDG].swap(ddg);
-  }
-  // PLAIN BYTE_ARRAY pages walked in segments when there are few of them (k_bin_walk_seg)
-  std::vector<uint64_t> segs;
-  std::vector<uint8_t> seg_page((size_t)std::max(n_pages, 1), 0);
-  if (!cls_lists[C_BINP].empty() && cls_lists[C_BINP].size() < pqg::BW_SEG_MAX_PAGES) {
-    for (int p : cls_lists[C_BINP]) {
-      const PageWork& w = P->h_work[(size_t)p];
-      if (plain_col[(size_t)w.column]) continue;  // one pass (k_bin_plain); the per-value fallback walks per page
-      const uint32_t nseg = (w.size + pqg::BW_SEG_BYTES - 1) / pqg::BW_SEG_BYTES + 1;  // + 1: tile alignment of the start
-      if (nseg < 3) continue;
-      seg_page[(size_t)p] = 1;
-      for (uint32_t k = 0; k < nseg; k++)
-        segs.push_back((uint64_t)(uint32_t)p | ((uint64_t)k << 32) | (k + 1 == nseg ? (1ull << 63) : 0ull));
-    }
-  }
-  // blen first: the part cleared before every launch (with the one-pass columns' last: not cleared
-  // while they take the one-pass path)
-  for (int pass = 0; pass < 2; pass++) {
-    for (int i = 0; i < n_cols; i++) {
-      if (ids_mode(cols[i]) || dict_direct[(size_t)i] || (plain_col[(size_t)i] != 0) != (pass == 1))
-        continue;  // ids go straight to the values; dictionary-direct columns store none
-      if (bin_out(cols[i]) || needs_ids[(size_t)i] || dba_fixed[(size_t)i])
-        blen_off[(size_t)i] = take(4 * (slot_acc[(size_t)i] + 1));
-    }
-    if (pass == 0) {
-      if (!segs.empty()) P->seg_status_off = take(8 * (segs.size() + 1));  // + the ticket counter
-      if (!pcp.empty()) P->pticket_off = take(8);
-      P->blen_bytes_nf = sc;
-    }
-  }
-  P->blen_bytes = sc;
-  // dictionary-direct columns: compact ids (u8 for dictionaries of at most 256 entries, else u16), written
-  // by k_dict_fused_dd for every slot k_dd_str reads (not cleared; padded: k_dd_str reads whole dwords)
-  for (int i = 0; i < n_cols; i++)
-    if (dict_direct[(size_t)i])
-      blen_off[(size_t)i] = take((cols[i].dict_num_values <= 256 && !dd_glob[(size_t)i] ? 1u : 2u) * (slot_acc[(size_t)i] + 16));
-  if (!pcp.empty()) P->pflag_off = take(8);
-  if (P->null_hints) P->hint_off = take(8);
-  if (!segs.empty()) P->seg_tmp_off = take(4 * 2 * (uint64_t)pqg::BW_SEG_CAP * segs.size());
-  P->n_segs = (uint32_t)segs.size();
-  for (int i = 0; i < n_cols; i++) {
-    if (dba_fixed[(size_t)i]) bsrc_off[(size_t)i] = take(4 * (slot_acc[(size_t)i] + 1));  // prefix lengths
-    if (dba_carry[(size_t)i]) carry_cols.push_back(i);
-  }
-  for (int i0 = 0; i0 < 2 * n_cols; i0++) {  // the one-pass columns last
-    const int i = i0 % n_cols;
-    if (!bin_out(cols[i]) || (plain_col[(size_t)i] != 0) != (i0 >= n_cols)) continue;
-    P->bin_capacity[(size_t)i] = cols[i].binary_capacity;
-    if (dict_direct[(size_t)i]) {  // the byte total (k_dd_bases) and the dictionary's entries only
-      P->bin_total_off[(size_t)i] = take(8);
-      // (dictionaries gathered from HBM: always the tile walk, whose scatter also packs their entries)
-      ((cols[i].dict_size >= pqg::DENT_MIN || dd_glob[(size_t)i]) && cols[i].dict_num_values ? dent_cols : dict_walk)
-          .push_back(i);
-      if (dd_glob[(size_t)i]) dent_off[(size_t)i] = take(8 * ((uint64_t)cols[i].dict_num_values + 1));
-      dlen_off[(size_t)i] = take(4 * ((uint64_t)cols[i].dict_num_values + 1));
-      dsrc_off[(size_t)i] = take(4 * ((uint64_t)cols[i].dict_num_values + 1));
-      continue;
-    }
-    bin_cols.push_back(i);
-    bsrc_off[(size_t)i] = take(4 * (slot_acc[(size_t)i] + 1));
-    const uint64_t nb = (slot_acc[(size_t)i] + pqg::SCAN_BLOCK - 1) / pqg::SCAN_BLOCK;
-    bsum_off[(size_t)i] = take(8 * (nb + 1));
-    P->bin_total_off[(size_t)i] = take(8);
-    for (uint64_t b = 0; b < nb; b++) bin_blocks.push_back(((uint64_t)(uint32_t)i << 32) | b);
-    if (nb == 0 && cols[i].values) P->empty_bin_values.push_back(cols[i].values);
-    if (cols[i].dict_offset >= 0 && !col_err[(size_t)i]) {
-      (cols[i].dict_size >= pqg::DENT_MIN && cols[i].dict_num_values ? dent_cols : dict_walk).push_back(i);
-      dlen_off[(size_t)i] = take(4 * ((uint64_t)cols[i].dict_num_values + 1));
-      dsrc_off[(size_t)i] = take(4 * ((uint64_t)cols[i].dict_num_values + 1));
-    }
-  }
-  {  // bin_cols / bin_blocks of the one-pass columns form the tails
-    int nf = 0;
-    for (int c : bin_cols) nf += plain_col[(size_t)c] ? 0 : 1;
-    P->n_bin_cols_nf = nf;
-    uint32_t nb = 0;
-    for (uint64_t b : bin_blocks) nb += plain_col[(size_t)(b >> 32)] ? 0 : 1;
-    P->n_bin_blocks_nf = nb;
-  }
-  std::vector<uint64_t> plain_chunks;  // copy chunks of the one-pass columns (per-value fallback only)
-  for (int k : {C_IDS, C_BINP, C_DLBA})
-    for (int p : cls_lists[(size_t)k]) {
-      const PageWork& w = P->h_work[(size_t)p];
-      if (k == C_BINP && plain_col[(size_t)w.column]) {
-        const uint32_t nch = (w.num_slots + pqg::CP_CHUNK_VALUES - 1) / pqg::CP_CHUNK_VALUES;
-        for (uint32_t j = 0; j < nch; j++) plain_chunks.push_back((uint64_t)(uint32_t)p | ((uint64_t)j << 32));
-        continue;
-      }
-      if (k == C_IDS && ids_mode(cols[w.column])) continue;  // the ids are the output
-      if (k == C_IDS && dict_direct[(size_t)w.column]) continue;  // the offset scan writes the bytes
-      if (k == C_IDS && cols[w.column].physical_type != PQG_BYTE_ARRAY) {
-        fixd.push_back(p);
-        continue;
-      }
-      if (k == C_IDS) bind.push_back(p);
-      const uint32_t nch = (w.num_slots + pqg::CP_CHUNK_VALUES - 1) / pqg::CP_CHUNK_VALUES;
-      for (uint32_t j = 0; j < nch; j++) bin_chunks.push_back((uint64_t)(uint32_t)p | ((uint64_t)j << 32));
-    }
-  P->n_bin_chunks_nf = (uint32_t)bin_chunks.size();
-  bin_chunks.insert(bin_chunks.end(), plain_chunks.begin(), plain_chunks.end());
-  {  // PLAIN pages: walked by k_bin_walk_seg (not listed), one wave per page, the one-pass columns last
-    std::vector<int> keep, tail, seg;
-    for (int p : cls_lists[C_BINP]) {
-      if (plain_col[(size_t)P->h_work[(size_t)p].column]) tail.push_back(p);
-      else if (!seg_page[(size_t)p]) keep.push_back(p);
-      else seg.push_back(p);
-    }
-    P->n_binp_fused = (int)tail.size();
-    P->n_binp_seg = (int)seg.size();
-    keep.insert(keep.end(), tail.begin(), tail.end());
-    keep.insert(keep.end(), seg.begin(), seg.end());
-    cls_lists[C_BINP].swap(keep);
-  }
-  // ---- DELTA_BYTE_ARRAY pages: BIN_CHUNK-value chunks (upper bound from the slot count)
-  std::vector<uint64_t> dba_chunks;
-  for (int p : cls_lists[C_DBA]) {
-    PageWork& w = P->h_work[(size_t)p];
-    w.chunk_base = (uint32_t)dba_chunks.size();
-    w.reserved = 0;
-    const uint32_t nch = (w.num_slots + pqg::BIN_CHUNK - 1) / pqg::BIN_CHUNK;
-    for (uint32_t j = 0; j < nch; j++) dba_chunks.push_back((uint64_t)(uint32_t)p | ((uint64_t)j << 32));
-  }
-  if (!dba_chunks.empty()) P->dba_meta_off = take(8 * dba_chunks.size());
-  P->n_dba_chunks = (uint32_t)dba_chunks.size();
-  // ---- dictionary pages: run-record capacity (a run covers >= 1 value and its header takes
-  // >= 1 byte) and output chunks (slots [j*CH, (j+1)*CH) of the page, upper bound from the slot count)
-  std::vector<uint64_t> chunk_list;
-  uint64_t rec_total = 0;
-  uint32_t chunk_total = 0;
-  for (int k = C_DICT4; k < C_DICT4 + N_DICT_CLS; k++) {
-    P->chunk_off[k - C_DICT4] = (uint32_t)chunk_list.size();
-    for (int p : cls_lists[(size_t)k]) {
-      PageWork& w = P->h_work[(size_t)p];
-      const int ew = k == C_DICT8 ? 8 : 4;
-      const uint32_t ch = pqg::dict_chunk_values(ew);
-      w.rec_base = rec_total;
-      rec_total += (uint64_t)std::min<uint32_t>(w.num_slots, w.size) + 1;
-      w.chunk_base = chunk_total;
-      const uint32_t nch = (uint32_t)(((uint64_t)w.num_slots + (uint32_t)(16 / ew) - 1 + ch - 1) / ch);
-      for (uint32_t j = 0; j < nch; j++) chunk_list.push_back((uint64_t)(uint32_t)p | ((uint64_t)j << 32));
-      chunk_total += nch;
-    }
-    P->chunk_n[k - C_DICT4] = (uint32_t)chunk_list.size() - P->chunk_off[k - C_DICT4];
-  }
-  std::vector<int32_t> dd_cols[2], dd_start[2];
-  for (int g = 0; g < 2; g++) {  // C_DD, then C_DDG
-    P->dd_chunk_off[g] = (uint32_t)chunk_list.size();
-    for (int p : cls_lists[g ? C_DDG : C_DD]) {  // (sorted by column)
-      PageWork& w = P->h_work[(size_t)p];
-      if (dd_cols[g].empty() || dd_cols[g].back() != w.column) {  // dd_start: [begin, end) of each column's chunks
-        if (!dd_cols[g].empty()) dd_start[g].push_back((int32_t)(chunk_list.size() - P->dd_chunk_off[g]));
-        while ((chunk_list.size() - P->dd_chunk_off[g]) % (uint32_t)pqg::DICT_WPB) {  // whole workgroups per column
-          chunk_list.push_back(0xFFFFFFFFull);
-          chunk_total++;
-        }
-        dd_cols[g].push_back(w.column);
-        dd_start[g].push_back((int32_t)(chunk_list.size() - P->dd_chunk_off[g]));
-        const pqg_column_desc& cc = cols[w.column];
-        if (!g)
-          P->dd_region = std::max<uint32_t>(P->dd_region, (uint32_t)(((uint64_t)cc.dict_size + 15u) & ~15ull) +
-                                                              4u * (uint32_t)cc.dict_num_values);
-      }
-      const uint32_t ch = pqg::dict_chunk_values(4);
-      w.rec_base = rec_total;
-      rec_total += (uint64_t)std::min<uint32_t>(w.num_slots, w.size) + 1;
-      w.chunk_base = chunk_total;
-      const uint32_t nch = (uint32_t)(((uint64_t)w.num_slots + 3u + ch - 1) / ch);
-      for (uint32_t j = 0; j < nch; j++) chunk_list.push_back((uint64_t)(uint32_t)p | ((uint64_t)j << 32));
-      chunk_total += nch;
-    }
-    if (!dd_cols[g].empty()) dd_start[g].push_back((int32_t)(chunk_list.size() - P->dd_chunk_off[g]));
-    P->dd_chunk_n[g] = (uint32_t)chunk_list.size() - P->dd_chunk_off[g];
-    P->n_dd_cols[g] = (int)dd_cols[g].size();
-    if (P->dd_chunk_n[g]) P->dd_sums_off[g] = take(8 * (uint64_t)P->dd_chunk_n[g]);
-  }
-  // ---- flatten lists: [levels][class 0]...[class n]
-  std::vector<int32_t> flat(lvl_list.begin(), lvl_list.end());
-  P->levels_off = 0;
-  P->levels_n = (int)lvl_list.size();
-  P->cls_off.assign(C_NCLS, 0);
-  P->cls_n.assign(C_NCLS, 0);
-  for (int k = 0; k < C_NCLS; k++) {
-    P->cls_off[(size_t)k] = (int)flat.size();
-    P->cls_n[(size_t)k] = (int)cls_lists[(size_t)k].size();
-    flat.insert(flat.end(), cls_lists[(size_t)k].begin(), cls_lists[(size_t)k].end());
-  }
-  std::vector<int32_t> cp, cps;
-  cps.push_back(0);
-  for (int i = 0; i < n_cols; i++) {
-    if (col_pages[(size_t)i].empty()) continue;
-    cp.insert(cp.end(), col_pages[(size_t)i].begin(), col_pages[(size_t)i].end());
-    cps.push_back((int32_t)cp.size());
-  }
-  P->n_scan_cols = (int)cps.size() - 1;
-  // bin_lists: [dictionary walks (columns)][BYTE_ARRAY dictionary pages][FLBA/INT96 dictionary pages][BYTE_ARRAY columns]
-  std::vector<int32_t> bl;
-  P->off_dict_walk = (int)bl.size(); P->n_dict_walk = (int)dict_walk.size(); bl.insert(bl.end(), dict_walk.begin(), dict_walk.end());
-  P->off_bind = (int)bl.size(); P->n_bind = (int)bind.size(); bl.insert(bl.end(), bind.begin(), bind.end());
-  P->off_fixd = (int)bl.size(); P->n_fixd = (int)fixd.size(); bl.insert(bl.end(), fixd.begin(), fixd.end());
-  P->off_bin_cols = (int)bl.size(); P->n_bin_cols = (int)bin_cols.size(); bl.insert(bl.end(), bin_cols.begin(), bin_cols.end());
-  P->off_carry = (int)bl.size(); P->n_carry = (int)carry_cols.size(); bl.insert(bl.end(), carry_cols.begin(), carry_cols.end());
-  std::vector<uint64_t> dent_tiles;
-  {  // large BYTE_ARRAY dictionaries: 2 KiB tiles of their pages, per column in dent_cols order
-    std::vector<int32_t> dstart(1, 0);
-    for (int i : dent_cols) {
-      const uint32_t nt = (cols[i].dict_size + pqg::DENT_TILE - 1) / pqg::DENT_TILE;
-      for (uint32_t t = 0; t < nt; t++) dent_tiles.push_back((uint64_t)(uint32_t)i | ((uint64_t)t << 32));
-      dstart.push_back((int32_t)dent_tiles.size());
-    }
-    P->off_dent_cols = (int)bl.size(); P->n_dent_cols = (int)dent_cols.size(); bl.insert(bl.end(), dent_cols.begin(), dent_cols.end());
-    P->off_dent_start = (int)bl.size(); bl.insert(bl.end(), dstart.begin(), dstart.end());
-    P->n_dent_tiles = (uint32_t)dent_tiles.size();
-    if (P->n_dent_tiles) {
-      P->dent_rec_off = take(16ull * P->n_dent_tiles);
-      P->dent_scr_off = take(2ull * pqg::DENT_CAP * P->n_dent_tiles);
-      P->dent_tb_off = take(8ull * P->n_dent_tiles);
-    }
-  }
-  for (int g = 0; g < 2; g++) {
-    P->off_dd_cols[g] = (int)bl.size(); bl.insert(bl.end(), dd_cols[g].begin(), dd_cols[g].end());
-    P->off_dd_start[g] = (int)bl.size(); bl.insert(bl.end(), dd_start[g].begin(), dd_start[g].end());
-  }
-  P->n_bin_blocks = (uint32_t)bin_blocks.size();
-  P->n_bin_chunks = (uint32_t)bin_chunks.size();
-  // ---- upload
+  P->dict_fused = ctx->dict_fused;
+  P->plain_fused = L.n_pcp != 0;
+  P->null_hints = L.null_hints;
+  // ---- allocation. The minimum sizes and slack terms are what the kernels read past the tables' ends.
+  const size_t pages1 = (size_t)std::max(n_pages, 1);
+  const PlanBufInit init[B_COUNT] = {
+      uploaded(B_WORK, L.h_work, 0),
+      uploaded(B_COLS, L.cols, 0),
+      uploaded(B_LISTS, L.flat, 1),
+      uploaded(B_COL_PAGES, L.cp, 1),
+      uploaded(B_COL_PAGE_START, L.cps, 0),
+      {B_ERR, nullptr, 0, err_region_bytes(n_pages, n_cols) + 16, false},
+      {B_BSCRATCH, nullptr, 0, (size_t)std::max<uint64_t>(L.scratch_bytes, 256), false},
+      uploaded(B_BIN_LISTS, L.bl, 1),
+      uploaded(B_BIN_BLOCKS, L.bin_blocks, 1),
+      uploaded(B_BIN_CHUNKS, L.bin_chunks, 1),
+      uploaded(B_DBA_CHUNKS, L.dba_chunks, 1),
+      uploaded(B_SEGS, L.segs, 1),
+      uploaded(B_DENT_TILES, L.dent_tiles, 1),
+      uploaded(B_PSEGS, L.psegs, 1),
+      {B_PSTATUS, nullptr, 2 * sizeof(uint64_t) * L.psegs.size(), 2 * sizeof(uint64_t) * std::max<size_t>(L.psegs.size(), 1), true},
+      uploaded(B_PCOL_PAGES, L.pcp, 1),
+      {B_PCOL_START, L.pcs.data(), L.pcp.empty() ? 0 : sizeof(int32_t) * L.pcs.size(), sizeof(int32_t) * L.pcs.size(), false},
+      // the expansion prefetches a page's first 128 records
+      {B_REC, nullptr, 0, sizeof(uint64_t) * (size_t)(L.rec_total + 2 * 64 + 16), false},
+      {B_CHUNK_RUN, nullptr, 0, sizeof(uint32_t) * std::max<uint32_t>(L.chunk_total, 1), false},
+      uploaded(B_CHUNKS, L.chunk_list, 1),
+      {B_PSTAT, nullptr, 0, sizeof(uint64_t) * pages1, false},
+      {B_FLAGS, nullptr, sizeof(uint32_t) * pages1, sizeof(uint32_t) * pages1, true},
+  };
   hipStream_t s = ctx->stream;
-  bool ok = P->work.ensure(sizeof(PageWork) * P->h_work.size()) == hipSuccess &&
-            P->cols.ensure(sizeof(ColumnDev) * hc.size()) == hipSuccess &&
-            P->lists.ensure(sizeof(int32_t) * std::max<size_t>(flat.size(), 1)) == hipSuccess &&
-            P->col_pages.ensure(sizeof(int32_t) * std::max<size_t>(cp.size(), 1)) == hipSuccess &&
-            P->col_page_start.ensure(sizeof(int32_t) * cps.size()) == hipSuccess &&
-            P->err.ensure(err_region_bytes(n_pages, n_cols) + 16) == hipSuccess &&
-            P->bscratch.ensure(std::max<uint64_t>(sc, 256)) == hipSuccess &&
-            P->bin_lists.ensure(sizeof(int32_t) * std::max<size_t>(bl.size(), 1)) == hipSuccess &&
-            P->bin_blocks.ensure(sizeof(uint64_t) * std::max<size_t>(bin_blocks.size(), 1)) == hipSuccess &&
-            P->bin_chunks.ensure(sizeof(uint64_t) * std::max<size_t>(bin_chunks.size(), 1)) == hipSuccess &&
-            P->dba_chunks.ensure(sizeof(uint64_t) * std::max<size_t>(dba_chunks.size(), 1)) == hipSuccess &&
-            P->segs.ensure(sizeof(uint64_t) * std::max<size_t>(segs.size(), 1)) == hipSuccess &&
-            P->dent_tiles.ensure(sizeof(uint64_t) * std::max<size_t>(dent_tiles.size(), 1)) == hipSuccess &&
-            P->psegs.ensure(sizeof(uint64_t) * std::max<size_t>(psegs.size(), 1)) == hipSuccess &&
-            P->pstatus.ensure(2 * sizeof(uint64_t) * std::max<size_t>(psegs.size(), 1)) == hipSuccess &&
-            P->pcol_pages.ensure(sizeof(int32_t) * std::max<size_t>(pcp.size(), 1)) == hipSuccess &&
-            P->pcol_start.ensure(sizeof(int32_t) * pcs.size()) == hipSuccess &&
-
-            P->rec.ensure(sizeof(uint64_t) * (rec_total + 2 * 64 + 16)) == hipSuccess &&  // the expansion prefetches a page's first 128
-            P->chunk_run.ensure(sizeof(uint32_t) * std::max<uint32_t>(chunk_total, 1)) == hipSuccess &&
-            P->chunks.ensure(sizeof(uint64_t) * std::max<size_t>(chunk_list.size(), 1)) == hipSuccess &&
-            P->pstat.ensure(sizeof(uint64_t) * (size_t)std::max(n_pages, 1)) == hipSuccess &&
-            P->flags.ensure(sizeof(uint32_t) * (size_t)std::max(n_pages, 1)) == hipSuccess;
-  ok = ok && hipMemsetAsync(P->flags.p, 0, sizeof(uint32_t) * (size_t)std::max(n_pages, 1), s) == hipSuccess;
-  {
-    uint8_t* scb = (uint8_t*)P->bscratch.p;
-    auto at = [&](uint64_t o) -> void* { return o == ~0ull ? nullptr : (void*)(scb + o); };
-    for (int i = 0; i < n_cols; i++) {
-      ColumnDev& d = hc[(size_t)i];
-      d.blen = ids_mode(cols[i]) ? (uint32_t*)cols[i].values : (uint32_t*)at(blen_off[(size_t)i]);
-      d.bsrc = (uint32_t*)at(bsrc_off[(size_t)i]);
-      d.dict_len = (uint32_t*)at(dlen_off[(size_t)i]);
-      d.dict_src = (uint32_t*)at(dsrc_off[(size_t)i]);
-      d.dict_ent = (uint64_t*)at(dent_off[(size_t)i]);
-      d.block_sums = (uint64_t*)at(bsum_off[(size_t)i]);
-      d.bin_total = (uint64_t*)at(P->bin_total_off[(size_t)i]);
-      d.n_slots = slot_acc[(size_t)i];
-      d.dict_direct = dict_direct[(size_t)i] ? (cols[i].dict_num_values <= 256 && !dd_glob[(size_t)i] ? 1u : 2u) : 0u;  // id bytes
-      d.dd_global = dd_glob[(size_t)i];
-      if (dba_fixed[(size_t)i]) {  // DELTA_BYTE_ARRAY values go straight to the fixed-width output
-        d.binary_data = (uint8_t*)cols[i].values;
-        d.binary_capacity = slot_acc[(size_t)i] * (uint64_t)d.elem_width;
-      }
-    }
+  bool ok = true;
+  for (const PlanBufInit& b : init) ok = ok && P->buf[b.buf].ensure(b.alloc) == hipSuccess;
+  // ---- the columns' scratch pointers
+  uint8_t* scb = (uint8_t*)P->buf[B_BSCRATCH].p;
+  auto resolve = [&](auto*& ptr, uint64_t off) {
+    if (off != pqg::NO_REGION) ptr = (std::remove_reference_t<decltype(ptr)>)(scb + off);
+  };
+  for (int i = 0; i < n_cols && ok; i++) {
+    ColumnDev& d = L.cols[(size_t)i];
+    resolve(d.blen, L.blen_off[(size_t)i]);  // (dictionary-id columns: the planner pointed it at `values`)
+    resolve(d.bsrc, L.bsrc_off[(size_t)i]);
+    resolve(d.dict_len, L.dlen_off[(size_t)i]);
+    resolve(d.dict_src, L.dsrc_off[(size_t)i]);
+    resolve(d.dict_ent, L.dent_off[(size_t)i]);
+    resolve(d.block_sums, L.bsum_off[(size_t)i]);
+    resolve(d.bin_total, L.bin_total_off[(size_t)i]);
   }
-  if (!bl.empty())
-    ok = ok && hipMemcpyAsync(P->bin_lists.p, bl.data(), sizeof(int32_t) * bl.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (!bin_blocks.empty())
-    ok = ok && hipMemcpyAsync(P->bin_blocks.p, bin_blocks.data(), sizeof(uint64_t) * bin_blocks.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (!bin_chunks.empty())
-    ok = ok && hipMemcpyAsync(P->bin_chunks.p, bin_chunks.data(), sizeof(uint64_t) * bin_chunks.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (!segs.empty())
-    ok = ok && hipMemcpyAsync(P->segs.p, segs.data(), sizeof(uint64_t) * segs.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (!dent_tiles.empty())
-    ok = ok && hipMemcpyAsync(P->dent_tiles.p, dent_tiles.data(), sizeof(uint64_t) * dent_tiles.size(), hipMemcpyHostToDevice,
-                              s) == hipSuccess;
-  if (!psegs.empty()) {
-    ok = ok && hipMemcpyAsync(P->psegs.p, psegs.data(), sizeof(uint64_t) * psegs.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-    ok = ok && hipMemsetAsync(P->pstatus.p, 0, 2 * sizeof(uint64_t) * psegs.size(), s) == hipSuccess;
+  // ---- upload
+  for (const PlanBufInit& b : init) {
+    if (!ok || !b.bytes) continue;
+    ok = (b.zero ? hipMemsetAsync(P->buf[b.buf].p, 0, b.bytes, s)
+                 : hipMemcpyAsync(P->buf[b.buf].p, b.host, b.bytes, hipMemcpyHostToDevice, s)) == hipSuccess;
   }
-  if (!pcp.empty()) {
-    ok = ok && hipMemcpyAsync(P->pcol_pages.p, pcp.data(), sizeof(int32_t) * pcp.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-    ok = ok && hipMemcpyAsync(P->pcol_start.p, pcs.data(), sizeof(int32_t) * pcs.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-    ok = ok && hipMemsetAsync((uint8_t*)P->bscratch.p + P->pflag_off, 0, 8, s) == hipSuccess;
-  }
-  if (P->null_hints) ok = ok && hipMemsetAsync((uint8_t*)P->bscratch.p + P->hint_off, 0, 8, s) == hipSuccess;
-  P->n_psegs = (uint32_t)psegs.size();
-  P->n_pcols = (int)pcs.size() - 1;
-  P->plain_fused = !pcp.empty();
-  P->n_pcp = (int)pcp.size();
-  if (!dba_chunks.empty())
-    ok = ok && hipMemcpyAsync(P->dba_chunks.p, dba_chunks.data(), sizeof(uint64_t) * dba_chunks.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (!chunk_list.empty())
-    ok = ok && hipMemcpyAsync(P->chunks.p, chunk_list.data(), sizeof(uint64_t) * chunk_list.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  ok = ok && hipMemcpyAsync(P->work.p, P->h_work.data(), sizeof(PageWork) * P->h_work.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  ok = ok && hipMemcpyAsync(P->cols.p, hc.data(), sizeof(ColumnDev) * hc.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (!flat.empty()) ok = ok && hipMemcpyAsync(P->lists.p, flat.data(), sizeof(int32_t) * flat.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  if (!cp.empty()) ok = ok && hipMemcpyAsync(P->col_pages.p, cp.data(), sizeof(int32_t) * cp.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  ok = ok && hipMemcpyAsync(P->col_page_start.p, cps.data(), sizeof(int32_t) * cps.size(), hipMemcpyHostToDevice, s) == hipSuccess;
-  // the host vectors above die at return: wait for the copies
+  // the epoch-tagged words of bscratch
+  if (ok && L.n_pcp) ok = hipMemsetAsync(scb + L.pflag_off, 0, 8, s) == hipSuccess;
+  if (ok && L.null_hints) ok = hipMemsetAsync(scb + L.hint_off, 0, 8, s) == hipSuccess;
+  // the copies read the layout's host tables, which live as long as the plan; one wait all the same, so
+  // that a failed copy is reported here
   ok = ok && hipStreamSynchronize(s) == hipSuccess;
   if (!ok) {
     set_status(st, PQG_ERR_HIP, -1, -1, "plan upload");
     pqg_plan_destroy(P);
     return PQG_ERR_HIP;
   }
-  P->kernels = count_kernels(P);
+  P->kernels = plan_kernels(P);
   *out = P;
   return PQG_OK;
 }
@@ -1080,54 +491,54 @@ int pqg_plan_launch(pqg_plan* P) {
   if (!P) return PQG_ERR_INVALID_ARG;
   pqg_ctx* ctx = P->ctx;
   hipStream_t s = ctx->stream;
-  uint64_t* err = (uint64_t*)P->err.p;
+  uint64_t* err = (uint64_t*)P->buf[B_ERR].p;
   // error words and the error counter share one allocation; both are tagged with the launch's
   // error epoch (pqg::ErrCount), so the region is zeroed only when the epoch wraps
-  const size_t err_bytes = err_region_bytes(P->n_pages, P->n_cols);
+  const size_t err_bytes = err_region_bytes(P->L.n_pages, P->L.n_cols);
   if (++P->err_epoch > pqg::ERR_EPOCH_MAX) {
     P->err_epoch = 1;
-    if (hipMemsetAsync(P->err.p, 0, err_bytes + 16, s) != hipSuccess) return PQG_ERR_HIP;
-    if (P->n_pcp && hipMemsetAsync((uint8_t*)P->bscratch.p + P->pflag_off, 0, 8, s) != hipSuccess) return PQG_ERR_HIP;
-    if (P->null_hints && hipMemsetAsync((uint8_t*)P->bscratch.p + P->hint_off, 0, 8, s) != hipSuccess) return PQG_ERR_HIP;
+    if (hipMemsetAsync(P->buf[B_ERR].p, 0, err_bytes + 16, s) != hipSuccess) return PQG_ERR_HIP;
+    if (P->L.n_pcp && hipMemsetAsync((uint8_t*)P->buf[B_BSCRATCH].p + P->L.pflag_off, 0, 8, s) != hipSuccess) return PQG_ERR_HIP;
+    if (P->null_hints && hipMemsetAsync((uint8_t*)P->buf[B_BSCRATCH].p + P->L.hint_off, 0, 8, s) != hipSuccess) return PQG_ERR_HIP;
   }
-  const pqg::ErrCount ecount{(uint32_t*)((uint8_t*)P->err.p + err_bytes), P->err_epoch};
-  PageWork* work = (PageWork*)P->work.p;
-  const ColumnDev* cols = (const ColumnDev*)P->cols.p;
-  const int32_t* lists = (const int32_t*)P->lists.p;
+  const pqg::ErrCount ecount{(uint32_t*)((uint8_t*)P->buf[B_ERR].p + err_bytes), P->err_epoch};
+  PageWork* work = (PageWork*)P->buf[B_WORK].p;
+  const ColumnDev* cols = (const ColumnDev*)P->buf[B_COLS].p;
+  const int32_t* lists = (const int32_t*)P->buf[B_LISTS].p;
   const bool pf = P->plain_fused;
-  const uint64_t clear = pf ? P->blen_bytes_nf : P->blen_bytes;
-  if (clear && hipMemsetAsync(P->bscratch.p, 0, clear, s) != hipSuccess) return PQG_ERR_HIP;
+  const uint64_t clear = pf ? P->L.blen_bytes_nf : P->L.blen_bytes;
+  if (clear && hipMemsetAsync(P->buf[B_BSCRATCH].p, 0, clear, s) != hipSuccess) return PQG_ERR_HIP;
   if (pf && ++P->pseg_epoch > 255u) {  // k_bin_plain tile words are tagged with 1..255
     P->pseg_epoch = 1;
-    if (hipMemsetAsync(P->pstatus.p, 0, 2 * sizeof(uint64_t) * P->n_psegs, s) != hipSuccess) return PQG_ERR_HIP;
+    if (hipMemsetAsync(P->buf[B_PSTATUS].p, 0, 2 * sizeof(uint64_t) * P->L.n_psegs, s) != hipSuccess) return PQG_ERR_HIP;
   }
-  for (void* v : P->empty_bin_values)
+  for (void* v : P->L.empty_bin_values)
     if (hipMemsetAsync(v, 0, sizeof(int64_t), s) != hipSuccess) return PQG_ERR_HIP;
   // page ready flags compare against the launch epoch (even); a walker's early partial status is
   // flagged epoch - 1. Reset on wrap.
   P->epoch += 2;
   if (P->epoch == 0) {
     P->epoch = 2;
-    if (hipMemsetAsync(P->flags.p, 0, sizeof(uint32_t) * (size_t)std::max(P->n_pages, 1), s) != hipSuccess)
+    if (hipMemsetAsync(P->buf[B_FLAGS].p, 0, sizeof(uint32_t) * (size_t)std::max(P->L.n_pages, 1), s) != hipSuccess)
       return PQG_ERR_HIP;
   }
   hipError_t e = hipSuccess;
   // level-first order: k_levels + k_scan_offsets give the nullable pages' counts and offsets before any
   // value kernel; with V2 header null counts (null_hints) the host has them and k_levels only verifies
   // them, on the caller's stream beside the forked value kernels (launched after the fork below)
-  const bool hints = P->null_hints && P->levels_n;
-  const int32_t* bl = (const int32_t*)P->bin_lists.p;
+  const bool hints = P->null_hints && P->L.levels_n;
+  const int32_t* bl = (const int32_t*)P->buf[B_BIN_LISTS].p;
   auto launch_dent = [&](hipStream_t st) -> hipError_t {  // large dictionaries' entries, per 2 KiB tile
-    uint8_t* scb = (uint8_t*)P->bscratch.p;
-    return pqg::launch_dict_entries(st, P->d_bytes, P->n_bytes, cols, (const uint64_t*)P->dent_tiles.p, P->n_dent_tiles,
-                                    bl + P->off_dent_cols, bl + P->off_dent_start, P->n_dent_cols,
-                                    (uint64_t*)(scb + P->dent_rec_off), (uint16_t*)(scb + P->dent_scr_off),
-                                    (uint64_t*)(scb + P->dent_tb_off), P->n_pages, err, ecount);
+    uint8_t* scb = (uint8_t*)P->buf[B_BSCRATCH].p;
+    return pqg::launch_dict_entries(st, P->d_bytes, P->n_bytes, cols, (const uint64_t*)P->buf[B_DENT_TILES].p, P->L.n_dent_tiles,
+                                    bl + P->L.off_dent_cols, bl + P->L.off_dent_start, P->L.n_dent_cols,
+                                    (uint64_t*)(scb + P->L.dent_rec_off), (uint16_t*)(scb + P->L.dent_scr_off),
+                                    (uint64_t*)(scb + P->L.dent_tb_off), P->L.n_pages, err, ecount);
   };
   // every large dictionary's column dictionary-direct with HBM entries (C_DDG only): its tile walk runs
   // on a queue of its own from the start, beside the levels and the id walk (k_dict_fused_dd<DD_IDS>)
   bool dent_fork = false;
-  if (e == hipSuccess && P->n_dent_tiles && P->cls_n[C_DDG] && !P->cls_n[C_DD] && !P->cls_n[C_IDS] && !P->n_bind) {
+  if (e == hipSuccess && P->L.n_dent_tiles && P->L.cls_n[C_DDG] && !P->L.cls_n[C_DD] && !P->L.cls_n[C_IDS] && !P->L.n_bind) {
     dent_fork = (ctx->dent_stream || hipStreamCreateWithFlags(&ctx->dent_stream, hipStreamNonBlocking) == hipSuccess) &&
                 (ctx->ev_dent_fork || hipEventCreateWithFlags(&ctx->ev_dent_fork, hipEventDisableTiming) == hipSuccess) &&
                 (ctx->ev_dent || hipEventCreateWithFlags(&ctx->ev_dent, hipEventDisableTiming) == hipSuccess) &&
@@ -1140,16 +551,16 @@ int pqg_plan_launch(pqg_plan* P) {
   }
   auto launch_dict_walks = [&](hipStream_t st) -> hipError_t {
     hipError_t r = hipSuccess;
-    if (P->n_dict_walk)  // BYTE_ARRAY dictionary entries (PlainBinaryDictionary ctor)
-      r = pqg::launch_bin_walk(st, P->d_bytes, P->n_bytes, work, cols, bl + P->off_dict_walk, P->n_dict_walk, 1,
-                               P->n_pages, err, ecount);
-    if (r == hipSuccess && P->n_dent_tiles && !dent_fork) r = launch_dent(st);
+    if (P->L.n_dict_walk)  // BYTE_ARRAY dictionary entries (PlainBinaryDictionary ctor)
+      r = pqg::launch_bin_walk(st, P->d_bytes, P->n_bytes, work, cols, bl + P->L.off_dict_walk, P->L.n_dict_walk, 1,
+                               P->L.n_pages, err, ecount);
+    if (r == hipSuccess && P->L.n_dent_tiles && !dent_fork) r = launch_dent(st);
     return r;
   };
-  if (e == hipSuccess && P->levels_n && !hints) {
-    e = pqg::launch_levels(s, P->d_bytes, P->n_bytes, work, cols, lists + P->levels_off, P->levels_n, err, ecount, nullptr);
+  if (e == hipSuccess && P->L.levels_n && !hints) {
+    e = pqg::launch_levels(s, P->d_bytes, P->n_bytes, work, cols, lists + P->L.levels_off, P->L.levels_n, err, ecount, nullptr);
     if (e == hipSuccess)
-      e = pqg::launch_scan(s, work, (const int32_t*)P->col_pages.p, (const int32_t*)P->col_page_start.p, P->n_scan_cols);
+      e = pqg::launch_scan(s, work, (const int32_t*)P->buf[B_COL_PAGES].p, (const int32_t*)P->buf[B_COL_PAGE_START].p, P->L.n_scan_cols);
   }
   // The one-pass PLAIN BYTE_ARRAY kernel is latency / issue bound (~1 TB/s) and independent of the other
   // columns' kernels (most of them HBM bound): with other pages in the plan it runs on a second queue,
@@ -1157,10 +568,10 @@ int pqg_plan_launch(pqg_plan* P) {
   // The BYTE_ARRAY kernels of the other columns likewise go to a third queue when fixed-width columns'
   // kernels (HBM bound) are in the plan to share the chip with.
   bool fork = false, fork_bin = false, fork_fix = false;
-  const bool has_fixed = P->cls_n[C_DICT4] || P->cls_n[C_DICT8] || P->cls_n[C_PLAIN] || P->cls_n[C_BOOL] ||
-                         P->cls_n[C_RLEBOOL] || P->cls_n[C_DELTA4] || P->cls_n[C_DELTA8] || P->cls_n[C_BSS];
-  const bool has_bin = P->n_dict_walk || P->n_dent_tiles || P->cls_n[C_IDS] || P->cls_n[C_DD] || P->cls_n[C_DDG] || P->cls_n[C_BINP] - P->n_binp_seg - (pf ? P->n_binp_fused : 0) > 0 ||
-                       P->cls_n[C_DLBA] || P->cls_n[C_DBA] || P->n_segs;
+  const bool has_fixed = P->L.cls_n[C_DICT4] || P->L.cls_n[C_DICT8] || P->L.cls_n[C_PLAIN] || P->L.cls_n[C_BOOL] ||
+                         P->L.cls_n[C_RLEBOOL] || P->L.cls_n[C_DELTA4] || P->L.cls_n[C_DELTA8] || P->L.cls_n[C_BSS];
+  const bool has_bin = P->L.n_dict_walk || P->L.n_dent_tiles || P->L.cls_n[C_IDS] || P->L.cls_n[C_DD] || P->L.cls_n[C_DDG] || P->L.cls_n[C_BINP] - P->L.n_binp_seg - (pf ? P->L.n_binp_fused : 0) > 0 ||
+                       P->L.cls_n[C_DLBA] || P->L.cls_n[C_DBA] || P->L.n_segs;
   const bool want = e == hipSuccess && ((pf && (has_fixed || has_bin)) || (has_bin && has_fixed) ||
                                         (hints && (pf || has_bin || has_fixed)));
   const bool ev_ok = want && (ctx->ev_fork || hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) == hipSuccess) &&
@@ -1180,54 +591,54 @@ int pqg_plan_launch(pqg_plan* P) {
                (ctx->ev_join_fix || hipEventCreateWithFlags(&ctx->ev_join_fix, hipEventDisableTiming) == hipSuccess) &&
                hipStreamWaitEvent(ctx->fix_stream, ctx->ev_fork, 0) == hipSuccess;
   if (e == hipSuccess && hints)  // the level sections, verified against the header counts, beside the value kernels
-    e = pqg::launch_levels(s, P->d_bytes, P->n_bytes, work, cols, lists + P->levels_off, P->levels_n, err, ecount,
-                           (uint32_t*)((uint8_t*)P->bscratch.p + P->hint_off));
+    e = pqg::launch_levels(s, P->d_bytes, P->n_bytes, work, cols, lists + P->L.levels_off, P->L.levels_n, err, ecount,
+                           (uint32_t*)((uint8_t*)P->buf[B_BSCRATCH].p + P->L.hint_off));
   if (e == hipSuccess && pf) {  // PLAIN-only BYTE_ARRAY columns: one pass (after the levels: n_values, out_offset)
-    uint8_t* scb = (uint8_t*)P->bscratch.p;
-    uint64_t* ps = (uint64_t*)P->pstatus.p;
-    e = pqg::launch_bin_plain(fork ? ctx->side_stream : s, P->d_bytes, P->n_bytes, work, cols, (const int32_t*)P->pcol_pages.p,
-                              (const int32_t*)P->pcol_start.p, P->n_pcols, (const uint64_t*)P->psegs.p, P->n_psegs, ps,
-                              ps + P->n_psegs, (uint32_t*)(scb + P->pticket_off), P->pseg_epoch,
-                              (uint32_t*)(scb + P->pflag_off), P->err_epoch, err, ecount, P->plain_pg, P->n_pcp);
+    uint8_t* scb = (uint8_t*)P->buf[B_BSCRATCH].p;
+    uint64_t* ps = (uint64_t*)P->buf[B_PSTATUS].p;
+    e = pqg::launch_bin_plain(fork ? ctx->side_stream : s, P->d_bytes, P->n_bytes, work, cols, (const int32_t*)P->buf[B_PCOL_PAGES].p,
+                              (const int32_t*)P->buf[B_PCOL_START].p, P->L.n_pcols, (const uint64_t*)P->buf[B_PSEGS].p, P->L.n_psegs, ps,
+                              ps + P->L.n_psegs, (uint32_t*)(scb + P->L.pticket_off), P->pseg_epoch,
+                              (uint32_t*)(scb + P->L.pflag_off), P->err_epoch, err, ecount, P->L.plain_pg, P->L.n_pcp);
     if (fork && hipEventRecord(ctx->ev_join, ctx->side_stream) != hipSuccess) e = hipErrorUnknown;
   }
   const hipStream_t sb = fork_bin ? ctx->bin_stream : s;  // BYTE_ARRAY kernels of the other columns
   const hipStream_t sf = fork_fix ? ctx->fix_stream : s;  // fixed-width columns
   if (e == hipSuccess) e = launch_dict_walks(sb);
   for (int k = 0; k < C_NCLS && e == hipSuccess; k++) {
-    int n = P->cls_n[(size_t)k] - (k == C_BINP ? P->n_binp_seg + (pf ? P->n_binp_fused : 0) : 0);
+    int n = P->L.cls_n[k] - (k == C_BINP ? P->L.n_binp_seg + (pf ? P->L.n_binp_fused : 0) : 0);
     if (!n) continue;
-    const int32_t* l = lists + P->cls_off[(size_t)k];
+    const int32_t* l = lists + P->L.cls_off[k];
     switch (k) {
       case C_DICT4:
       case C_DICT8: {
         const int i = k - C_DICT4;
-        e = pqg::launch_dict(k == C_DICT8 ? 8 : 4, sf, P->d_bytes, P->n_bytes, work, cols, l, n, (uint64_t*)P->rec.p,
-                             (uint32_t*)P->chunk_run.p, (const uint64_t*)P->chunks.p + P->chunk_off[i], P->chunk_n[i],
-                             (uint64_t*)P->pstat.p, (uint32_t*)P->flags.p, P->epoch, P->dict_fused, err, ecount);
+        e = pqg::launch_dict(k == C_DICT8 ? 8 : 4, sf, P->d_bytes, P->n_bytes, work, cols, l, n, (uint64_t*)P->buf[B_REC].p,
+                             (uint32_t*)P->buf[B_CHUNK_RUN].p, (const uint64_t*)P->buf[B_CHUNKS].p + P->L.chunk_off[i], P->L.chunk_n[i],
+                             (uint64_t*)P->buf[B_PSTAT].p, (uint32_t*)P->buf[B_FLAGS].p, P->epoch, P->dict_fused, err, ecount);
         break;
       }
       case C_IDS: {
         const int i = k - C_DICT4;
-        e = pqg::launch_dict_ids(sb, P->d_bytes, P->n_bytes, work, cols, l, n, (uint64_t*)P->rec.p,
-                                 (uint32_t*)P->chunk_run.p, (const uint64_t*)P->chunks.p + P->chunk_off[i],
-                                 P->chunk_n[i], (uint64_t*)P->pstat.p, (uint32_t*)P->flags.p, P->epoch, P->dict_fused, err, ecount);
+        e = pqg::launch_dict_ids(sb, P->d_bytes, P->n_bytes, work, cols, l, n, (uint64_t*)P->buf[B_REC].p,
+                                 (uint32_t*)P->buf[B_CHUNK_RUN].p, (const uint64_t*)P->buf[B_CHUNKS].p + P->L.chunk_off[i],
+                                 P->L.chunk_n[i], (uint64_t*)P->buf[B_PSTAT].p, (uint32_t*)P->buf[B_FLAGS].p, P->epoch, P->dict_fused, err, ecount);
         break;
       }
       case C_DD:
       case C_DDG: {
         const int g = k == C_DDG ? 1 : 0;
-        e = pqg::launch_dict_dd(sb, P->d_bytes, P->n_bytes, work, cols, l, n, (uint64_t*)P->rec.p,
-                                (uint32_t*)P->chunk_run.p, (const uint64_t*)P->chunks.p + P->dd_chunk_off[g],
-                                P->dd_chunk_n[g], (uint64_t*)P->pstat.p, (uint32_t*)P->flags.p, P->epoch, P->dict_fused,
-                                err, ecount, (uint64_t*)((uint8_t*)P->bscratch.p + P->dd_sums_off[g]),
-                                bl + P->off_dd_cols[g], bl + P->off_dd_start[g], P->n_dd_cols[g], P->dd_region, g == 1,
+        e = pqg::launch_dict_dd(sb, P->d_bytes, P->n_bytes, work, cols, l, n, (uint64_t*)P->buf[B_REC].p,
+                                (uint32_t*)P->buf[B_CHUNK_RUN].p, (const uint64_t*)P->buf[B_CHUNKS].p + P->L.dd_chunk_off[g],
+                                P->L.dd_chunk_n[g], (uint64_t*)P->buf[B_PSTAT].p, (uint32_t*)P->buf[B_FLAGS].p, P->epoch, P->dict_fused,
+                                err, ecount, (uint64_t*)((uint8_t*)P->buf[B_BSCRATCH].p + P->L.dd_sums_off[g]),
+                                bl + P->L.off_dd_cols[g], bl + P->L.off_dd_start[g], P->L.n_dd_cols[g], P->L.dd_region, g == 1,
                                 g == 1 && dent_fork ? ctx->ev_dent : nullptr);
         break;
       }
       case C_BSS: e = pqg::launch_bss(sf, P->d_bytes, P->n_bytes, work, cols, l, n, err, ecount); break;
       case C_BINP:
-        e = pqg::launch_bin_walk(sb, P->d_bytes, P->n_bytes, work, cols, l, n, 0, P->n_pages, err, ecount);
+        e = pqg::launch_bin_walk(sb, P->d_bytes, P->n_bytes, work, cols, l, n, 0, P->L.n_pages, err, ecount);
         break;
       case C_DLBA: e = pqg::launch_dlba_lengths(sb, P->d_bytes, P->n_bytes, work, cols, l, n, err, ecount); break;
       case C_DBA:
@@ -1240,32 +651,32 @@ int pqg_plan_launch(pqg_plan* P) {
       case C_DELTA8: e = pqg::launch_delta(8, sf, P->d_bytes, P->n_bytes, work, cols, l, n, err, ecount); break;
     }
   }
-  if (e == hipSuccess && P->n_segs && !P->seg_walk)  // the segmented pages one wave each (after a timeout)
+  if (e == hipSuccess && P->L.n_segs && !P->seg_walk)  // the segmented pages one wave each (after a timeout)
     e = pqg::launch_bin_walk(sb, P->d_bytes, P->n_bytes, work, cols,
-                             lists + P->cls_off[C_BINP] + (P->cls_n[C_BINP] - P->n_binp_seg), P->n_binp_seg, 0,
-                             P->n_pages, err, ecount);
-  if (e == hipSuccess && P->n_segs && P->seg_walk) {  // PLAIN BYTE_ARRAY pages in segments (status + ticket cleared above)
-    uint8_t* scb = (uint8_t*)P->bscratch.p;
-    e = pqg::launch_bin_walk_seg(sb, P->d_bytes, P->n_bytes, work, cols, (const uint64_t*)P->segs.p, P->n_segs,
-                                 (uint64_t*)(scb + P->seg_status_off), (uint32_t*)(scb + P->seg_status_off) + 2u * P->n_segs,
-                                 (uint32_t*)(scb + P->seg_tmp_off), err, ecount);
+                             lists + P->L.cls_off[C_BINP] + (P->L.cls_n[C_BINP] - P->L.n_binp_seg), P->L.n_binp_seg, 0,
+                             P->L.n_pages, err, ecount);
+  if (e == hipSuccess && P->L.n_segs && P->seg_walk) {  // PLAIN BYTE_ARRAY pages in segments (status + ticket cleared above)
+    uint8_t* scb = (uint8_t*)P->buf[B_BSCRATCH].p;
+    e = pqg::launch_bin_walk_seg(sb, P->d_bytes, P->n_bytes, work, cols, (const uint64_t*)P->buf[B_SEGS].p, P->L.n_segs,
+                                 (uint64_t*)(scb + P->L.seg_status_off), (uint32_t*)(scb + P->L.seg_status_off) + 2u * P->L.n_segs,
+                                 (uint32_t*)(scb + P->L.seg_tmp_off), err, ecount);
   }
   // post-passes: dictionary ids -> BYTE_ARRAY entries / fixed-width entries; offsets; value bytes
-  if (e == hipSuccess && P->n_bind) e = pqg::launch_bin_dict_map(sb, work, cols, bl + P->off_bind, P->n_bind);
-  if (e == hipSuccess && P->n_fixd)
-    e = pqg::launch_gather_fixed(sb, P->d_bytes, P->n_bytes, work, cols, bl + P->off_fixd, P->n_fixd);
-  const uint32_t n_blocks = pf ? P->n_bin_blocks_nf : P->n_bin_blocks;
+  if (e == hipSuccess && P->L.n_bind) e = pqg::launch_bin_dict_map(sb, work, cols, bl + P->L.off_bind, P->L.n_bind);
+  if (e == hipSuccess && P->L.n_fixd)
+    e = pqg::launch_gather_fixed(sb, P->d_bytes, P->n_bytes, work, cols, bl + P->L.off_fixd, P->L.n_fixd);
+  const uint32_t n_blocks = pf ? P->L.n_bin_blocks_nf : P->L.n_bin_blocks;
   if (e == hipSuccess && n_blocks)
-    e = pqg::launch_bin_scan(sb, P->d_bytes, P->n_bytes, cols, bl + P->off_bin_cols, pf ? P->n_bin_cols_nf : P->n_bin_cols,
-                             (const uint64_t*)P->bin_blocks.p, n_blocks);
-  const uint32_t n_chunks = pf ? P->n_bin_chunks_nf : P->n_bin_chunks;
+    e = pqg::launch_bin_scan(sb, P->d_bytes, P->n_bytes, cols, bl + P->L.off_bin_cols, pf ? P->L.n_bin_cols_nf : P->L.n_bin_cols,
+                             (const uint64_t*)P->buf[B_BIN_BLOCKS].p, n_blocks);
+  const uint32_t n_chunks = pf ? P->L.n_bin_chunks_nf : P->L.n_bin_chunks;
   if (e == hipSuccess && n_chunks)
-    e = pqg::launch_bin_copy(sb, P->d_bytes, P->n_bytes, work, cols, (const uint64_t*)P->bin_chunks.p, n_chunks, err,
+    e = pqg::launch_bin_copy(sb, P->d_bytes, P->n_bytes, work, cols, (const uint64_t*)P->buf[B_BIN_CHUNKS].p, n_chunks, err,
                              ecount);
-  if (e == hipSuccess && P->cls_n[C_DBA])
-    e = pqg::launch_dba_copy(sb, P->d_bytes, P->n_bytes, work, cols, lists + P->cls_off[C_DBA], P->cls_n[C_DBA],
-                             (const uint64_t*)P->dba_chunks.p, P->n_dba_chunks, P->dba_meta(), bl + P->off_carry,
-                             P->n_carry, err, ecount);
+  if (e == hipSuccess && P->L.cls_n[C_DBA])
+    e = pqg::launch_dba_copy(sb, P->d_bytes, P->n_bytes, work, cols, lists + P->L.cls_off[C_DBA], P->L.cls_n[C_DBA],
+                             (const uint64_t*)P->buf[B_DBA_CHUNKS].p, P->L.n_dba_chunks, P->dba_meta(), bl + P->L.off_carry,
+                             P->L.n_carry, err, ecount);
   if (fork && hipStreamWaitEvent(s, ctx->ev_join, 0) != hipSuccess) e = hipErrorUnknown;
   if (fork_bin && (hipEventRecord(ctx->ev_join_bin, ctx->bin_stream) != hipSuccess ||
                    hipStreamWaitEvent(s, ctx->ev_join_bin, 0) != hipSuccess))
@@ -1287,28 +698,7 @@ int pqg_plan_destroy(pqg_plan* P) {
     auto& u = P->ctx->unsynced;
     u.erase(std::remove(u.begin(), u.end(), P), u.end());
   }
-  P->work.release();
-  P->cols.release();
-  P->lists.release();
-  P->col_pages.release();
-  P->col_page_start.release();
-  P->err.release();
-  P->rec.release();
-  P->chunk_run.release();
-  P->psegs.release();
-  P->pstatus.release();
-  P->pcol_pages.release();
-  P->pcol_start.release();
-  P->chunks.release();
-  P->pstat.release();
-  P->flags.release();
-  P->bscratch.release();
-  P->bin_lists.release();
-  P->bin_blocks.release();
-  P->bin_chunks.release();
-  P->dba_chunks.release();
-  P->segs.release();
-  P->dent_tiles.release();
+  for (DevBuf& b : P->buf) b.release();
   delete P;
   return PQG_OK;
 }
@@ -1328,21 +718,21 @@ int resolve_errors(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work_out)
   hipStream_t s = ctx->stream;
   if (ctx->pin_err.ensure(16) != hipSuccess) return PQG_ERR_HIP;
   uint32_t* cnt = (uint32_t*)ctx->pin_err.p;
-  if (hipMemcpyAsync(cnt, (uint8_t*)P->err.p + err_region_bytes(P->n_pages, P->n_cols), sizeof(uint32_t),
+  if (hipMemcpyAsync(cnt, (uint8_t*)P->buf[B_ERR].p + err_region_bytes(P->L.n_pages, P->L.n_cols), sizeof(uint32_t),
                      hipMemcpyDeviceToHost, s) != hipSuccess)
     return PQG_ERR_HIP;
   bool need_work = false;
-  for (auto v : P->col_nullable) need_work = need_work || v;
+  for (auto v : P->L.col_nullable) need_work = need_work || v;
   if (need_work && work_out) {
-    work_out->resize(P->h_work.size());
-    if (hipMemcpyAsync(work_out->data(), P->work.p, sizeof(PageWork) * P->h_work.size(), hipMemcpyDeviceToHost, s) != hipSuccess)
+    work_out->resize(P->L.h_work.size());
+    if (hipMemcpyAsync(work_out->data(), P->buf[B_WORK].p, sizeof(PageWork) * P->L.h_work.size(), hipMemcpyDeviceToHost, s) != hipSuccess)
       return PQG_ERR_HIP;
   }
   if (hipStreamSynchronize(s) != hipSuccess) return PQG_ERR_HIP;
   std::vector<uint64_t> errs;
   if (*cnt == P->err_epoch) {  // a kernel of the last launch reported (see pqg::ErrCount)
-    errs.resize(3 * (size_t)(P->n_pages + std::max(P->n_cols, 1)));
-    if (hipMemcpy(errs.data(), P->err.p, sizeof(uint64_t) * errs.size(), hipMemcpyDeviceToHost) != hipSuccess) return PQG_ERR_HIP;
+    errs.resize(3 * (size_t)(P->L.n_pages + std::max(P->L.n_cols, 1)));
+    if (hipMemcpy(errs.data(), P->buf[B_ERR].p, sizeof(uint64_t) * errs.size(), hipMemcpyDeviceToHost) != hipSuccess) return PQG_ERR_HIP;
     for (uint64_t& w : errs)  // words of earlier launches are stale: no error in this one
       w = (w >> 48) == P->err_epoch ? (~w & pqg::ERR_KEY_MASK) : ~0ull;
   }
@@ -1350,20 +740,20 @@ int resolve_errors(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work_out)
   if (rc) return rc;
   // BYTE_ARRAY output capacity (API misuse, after the decode errors: values past a decode error
   // are not meaningful and may inflate the byte count)
-  for (int i = 0; i < P->n_cols; i++) {
-    if (P->bin_total_off[(size_t)i] == ~0ull) continue;
+  for (int i = 0; i < P->L.n_cols; i++) {
+    if (P->L.bin_total_off[(size_t)i] == ~0ull) continue;
     uint64_t total = 0;
-    if (hipMemcpy(&total, (uint8_t*)P->bscratch.p + P->bin_total_off[(size_t)i], sizeof(total), hipMemcpyDeviceToHost) !=
+    if (hipMemcpy(&total, (uint8_t*)P->buf[B_BSCRATCH].p + P->L.bin_total_off[(size_t)i], sizeof(total), hipMemcpyDeviceToHost) !=
         hipSuccess)
       return PQG_ERR_HIP;
-    if (total > P->bin_capacity[(size_t)i]) {
+    if (total > P->L.bin_capacity[(size_t)i]) {
       if (st) {
         st->code = PQG_ERR_INVALID_ARG;
         st->page = -1;
         st->value_index = (int64_t)total;
         std::snprintf(st->message, sizeof(st->message),
                       "binary capacity: column %d needs %llu bytes of binary_data (capacity %llu)", i,
-                      (unsigned long long)total, (unsigned long long)P->bin_capacity[(size_t)i]);
+                      (unsigned long long)total, (unsigned long long)P->L.bin_capacity[(size_t)i]);
       }
       return PQG_ERR_INVALID_ARG;
     }
@@ -1373,20 +763,20 @@ int resolve_errors(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work_out)
 
 int resolve_page_errors(pqg_plan* P, pqg_status* st, const std::vector<uint64_t>& errs) {
   // every page's own first error (pqg_page_errors), then the batch's first in page order (st)
-  P->page_errs.assign((size_t)P->n_pages, pqg_page_error{PQG_OK, PQG_PHASE_NONE, -1});
-  if (P->host_errs.empty() && errs.empty()) return PQG_OK;
-  std::vector<const HostErr*> herr((size_t)std::max(P->n_pages, 1), nullptr);
-  for (const HostErr& h : P->host_errs)
+  P->page_errs.assign((size_t)P->L.n_pages, pqg_page_error{PQG_OK, PQG_PHASE_NONE, -1});
+  if (P->L.host_errs.empty() && errs.empty()) return PQG_OK;
+  std::vector<const HostErr*> herr((size_t)std::max(P->L.n_pages, 1), nullptr);
+  for (const HostErr& h : P->L.host_errs)
     if (!herr[(size_t)h.page]) herr[(size_t)h.page] = &h;
   int first = -1;
-  for (int p = 0; p < P->n_pages; p++) {
+  for (int p = 0; p < P->L.n_pages; p++) {
     pqg_page_error& pe = P->page_errs[(size_t)p];
     const HostErr* h = herr[(size_t)p];
     // device-detected dictionary page errors (BYTE_ARRAY dictionary walk, pseudo page n_pages + column):
     // the ColumnReaderBase ctor reads the dictionary before the column's first page
-    const int col = P->h_work[(size_t)p].column;
-    const uint64_t d = (!errs.empty() && col >= 0 && col < P->n_cols && P->col_first_page[(size_t)col] == p)
-                           ? errs[3 * (size_t)(P->n_pages + col)] : ~0ull;
+    const int col = P->L.h_work[(size_t)p].column;
+    const uint64_t d = (!errs.empty() && col >= 0 && col < P->L.n_cols && P->L.col_first_page[(size_t)col] == p)
+                           ? errs[3 * (size_t)(P->L.n_pages + col)] : ~0ull;
     uint64_t init = errs.empty() ? ~0ull : errs[3 * (size_t)p];
     uint64_t lvl = errs.empty() ? ~0ull : errs[3 * (size_t)p + 1];
     uint64_t val = errs.empty() ? ~0ull : errs[3 * (size_t)p + 2];
@@ -1427,23 +817,23 @@ namespace {
 // timeout re-run. `work` receives the plan's PageWork (nullable columns' value counts).
 int sync_plan(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work) {
   pqg_ctx* ctx = P->ctx;
-  if (P->null_hints && P->levels_n) {
+  if (P->null_hints && P->L.levels_n) {
     // A V2 header null count that disagrees with the page's definition levels (or a level error on such
     // a page): the value kernels ran on wrong counts / offsets. The reference decodes by the levels
     // (ColumnReaderBase.java:650-676, 760-771), so the launch is re-run level-first, which rewrites every
     // output; the plan keeps that order.
     uint32_t flag = 0;
-    if (hipMemcpy(&flag, (uint8_t*)P->bscratch.p + P->hint_off, sizeof(flag), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&flag, (uint8_t*)P->buf[B_BSCRATCH].p + P->L.hint_off, sizeof(flag), hipMemcpyDeviceToHost) != hipSuccess)
       return PQG_ERR_HIP;
     if (flag == P->err_epoch) {
       P->null_hints = false;
-      P->kernels = count_kernels(P);
+      P->kernels = plan_kernels(P);
       P->hint_fallbacks++;
       const int lrc = pqg_plan_launch(P);
       if (lrc != PQG_OK) return lrc;
       if (P->d_counts &&  // pqg_decode's per-page counts, copied after the first launch
-          hipMemcpy2DAsync(P->d_counts, sizeof(uint32_t), (const uint8_t*)P->work.p + offsetof(PageWork, n_values),
-                           sizeof(PageWork), sizeof(uint32_t), (size_t)P->n_pages, hipMemcpyDeviceToDevice,
+          hipMemcpy2DAsync(P->d_counts, sizeof(uint32_t), (const uint8_t*)P->buf[B_WORK].p + offsetof(PageWork, n_values),
+                           sizeof(PageWork), sizeof(uint32_t), (size_t)P->L.n_pages, hipMemcpyDeviceToDevice,
                            ctx->stream) != hipSuccess)
         return PQG_ERR_HIP;
       if (hipStreamSynchronize(ctx->stream) != hipSuccess) return PQG_ERR_HIP;
@@ -1454,11 +844,11 @@ int sync_plan(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work) {
     // breaks the one-pass path's byte bases: the launch is re-run on the per-value path (k_bin_walk,
     // offset scan, k_bin_copy), which reads exactly n_values values per page; the plan keeps that path.
     uint32_t flag = 0;
-    if (hipMemcpy(&flag, (uint8_t*)P->bscratch.p + P->pflag_off, sizeof(flag), hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&flag, (uint8_t*)P->buf[B_BSCRATCH].p + P->L.pflag_off, sizeof(flag), hipMemcpyDeviceToHost) != hipSuccess)
       return PQG_ERR_HIP;
     if (flag == P->err_epoch) {
       P->plain_fused = false;
-      P->kernels = count_kernels(P);
+      P->kernels = plan_kernels(P);
       P->plain_fallbacks++;
       const int lrc = pqg_plan_launch(P);
       if (lrc != PQG_OK) return lrc;
@@ -1469,7 +859,7 @@ int sync_plan(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work) {
   // only a timeout of the fused dictionary kernel's hand-off is re-run in split mode (a PLAIN
   // BYTE_ARRAY segment walk that timed out waiting for its predecessor reaches the caller)
   const int tpage = st ? (int)st->page : -1;
-  const int tcls = tpage >= 0 && tpage < P->n_pages ? P->page_cls[(size_t)tpage] : -1;
+  const int tcls = tpage >= 0 && tpage < P->L.n_pages ? P->L.page_cls[(size_t)tpage] : -1;
   if (rc == PQG_ERR_TIMEOUT && P->dict_fused && (tcls == C_DICT4 || tcls == C_DICT8 || tcls == C_IDS || tcls == C_DD || tcls == C_DDG)) {
     // The fused dictionary kernel's hand-off relies on the walker workgroups being dispatched before
     // the expansion workgroups that wait for them, which HIP does not promise. A launch in which an
@@ -1478,7 +868,7 @@ int sync_plan(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work) {
     // which have no inter-workgroup waits; the plan keeps that mode. Every output of the re-run is
     // written again, so the result is the same bit for bit.
     P->dict_fused = false;
-    P->kernels = count_kernels(P);
+    P->kernels = plan_kernels(P);
     P->timeout_fallbacks++;
     rc = pqg_plan_launch(P);
     if (rc == PQG_OK) {
@@ -1491,10 +881,10 @@ int sync_plan(pqg_plan* P, pqg_status* st, std::vector<PageWork>* work) {
   // predecessor's publication (k_bin_walk_seg; the predecessor always holds an earlier ticket, so this
   // needs a starved wave): the plan re-runs with those pages one wave each and keeps that mode
   const int tpage2 = st ? (int)st->page : -1;
-  const int tcls2 = tpage2 >= 0 && tpage2 < P->n_pages ? P->page_cls[(size_t)tpage2] : -1;
-  if (rc == PQG_ERR_TIMEOUT && P->n_segs && P->seg_walk && tcls2 == C_BINP) {
+  const int tcls2 = tpage2 >= 0 && tpage2 < P->L.n_pages ? P->L.page_cls[(size_t)tpage2] : -1;
+  if (rc == PQG_ERR_TIMEOUT && P->L.n_segs && P->seg_walk && tcls2 == C_BINP) {
     P->seg_walk = false;
-    P->kernels = count_kernels(P);
+    P->kernels = plan_kernels(P);
     P->timeout_fallbacks++;
     rc = pqg_plan_launch(P);
     if (rc == PQG_OK) {
@@ -1561,11 +951,11 @@ int pqg_sync(pqg_ctx* ctx, pqg_status* st) {
     }
     if (prc == PQG_ERR_HIP) break;
     if (ctx->last_cols && P == ctx->last) {
-      for (int i = 0; i < P->n_cols; i++) {
-        uint64_t n = P->col_required_values[(size_t)i];
-        if (P->col_nullable[(size_t)i] && !work.empty()) {
+      for (int i = 0; i < P->L.n_cols; i++) {
+        uint64_t n = P->L.col_required_values[(size_t)i];
+        if (P->L.col_nullable[(size_t)i] && !work.empty()) {
           n = 0;
-          for (int p = 0; p < P->n_pages; p++)
+          for (int p = 0; p < P->L.n_pages; p++)
             if (work[(size_t)p].column == i) n += work[(size_t)p].n_values;
         }
         ctx->last_cols[i].values_written = n;
@@ -1578,7 +968,7 @@ int pqg_sync(pqg_ctx* ctx, pqg_status* st) {
 }
 
 int pqg_plan_page_errors(pqg_plan* P, pqg_page_error* out, int n_pages) {
-  if (!P || n_pages != P->n_pages || (n_pages && !out)) return PQG_ERR_INVALID_ARG;
+  if (!P || n_pages != P->L.n_pages || (n_pages && !out)) return PQG_ERR_INVALID_ARG;
   for (int p = 0; p < n_pages; p++)
     out[p] = (size_t)p < P->page_errs.size() ? P->page_errs[(size_t)p] : pqg_page_error{PQG_OK, PQG_PHASE_NONE, -1};
   return PQG_OK;
@@ -1628,7 +1018,7 @@ static int decode_impl(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, u
   P->d_counts = n_pages > 0 ? d_page_value_counts : nullptr;
   if (rc == PQG_OK && d_page_value_counts && n_pages > 0) {
     // n_values of every page (strided in PageWork) -> dense uint32 array
-    rc = hipMemcpy2DAsync(d_page_value_counts, sizeof(uint32_t), (const uint8_t*)P->work.p + offsetof(PageWork, n_values),
+    rc = hipMemcpy2DAsync(d_page_value_counts, sizeof(uint32_t), (const uint8_t*)P->buf[B_WORK].p + offsetof(PageWork, n_values),
                           sizeof(PageWork), sizeof(uint32_t), (size_t)n_pages, hipMemcpyDeviceToDevice,
                           ctx->stream) == hipSuccess
              ? PQG_OK
@@ -1778,10 +1168,10 @@ static int host_path(pqg_ctx* ctx, const uint8_t* h_bytes, uint64_t n_bytes, pqg
     // binary capacity: size every BYTE_ARRAY column to the byte count the device produced
     bool grew = false;
     for (int i = 0; i < n_cols; i++) {
-      const uint64_t o = ctx->last->bin_total_off[(size_t)i];
+      const uint64_t o = ctx->last->L.bin_total_off[(size_t)i];
       if (o == ~0ull) continue;
       uint64_t t = 0;
-      if (hipMemcpy(&t, (uint8_t*)ctx->last->bscratch.p + o, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) return PQG_ERR_HIP;
+      if (hipMemcpy(&t, (uint8_t*)ctx->last->buf[B_BSCRATCH].p + o, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) return PQG_ERR_HIP;
       if (t > bin_cap[(size_t)i]) { bin_cap[(size_t)i] = t; grew = true; }
     }
     if (!grew) break;
