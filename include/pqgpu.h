@@ -256,6 +256,9 @@ void* pqg_ctx_stream(pqg_ctx* ctx);
  *   PQG_DISPATCH_GZIP_PREPASS_MIN pqg_gzip_decompress: pages of at least `value` output bytes take the
  *                                token pre-pass + replay, smaller ones the one-wave decoder (default
  *                                16384; 0 = every page); applies to later pqg_gzip_decompress calls
+ *   PQG_DISPATCH_ZSTD_PREPASS    pqg_zstd_decompress: 1 = lane-per-page sequence pre-pass + replay (default),
+ *                                0 = every page takes the inline sequence decoder (the pre-pass's
+ *                                fallback); applies to later pqg_zstd_decompress calls
  * Returns PQG_ERR_INVALID_ARG for an unknown key or value. Not thread-safe (like the ctx). */
 enum pqg_dispatch {
   PQG_DISPATCH_PLAIN_ONE_PASS = 1,
@@ -263,7 +266,8 @@ enum pqg_dispatch {
   PQG_DISPATCH_GZIP_PREPASS_MIN = 3,
   PQG_DISPATCH_DICT_FUSED = 4,
   PQG_DISPATCH_NULL_HINTS = 5,
-  PQG_DISPATCH_TAKE_STAGED = 6
+  PQG_DISPATCH_TAKE_STAGED = 6,
+  PQG_DISPATCH_ZSTD_PREPASS = 7
 };
 int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value);
 

@@ -9,6 +9,8 @@
  * Every case is decoded by pqr_decode into exactly-sized heap outputs (values, levels, BYTE_ARRAY
  * bytes of the capacity the case asks for), so an out-of-bounds read of the page bytes or write past
  * an output is caught. Prints "<file> rc=<code>" per case.
+ *   Zstandard case file (tests/test_zstd_build.py; link zstd_ref.c): "PQGZ" | u64 size asked | u64 n | frame bytes[n],
+ *   decompressed by pqr_zstd_decompress from an exactly-sized input into an exactly-sized output.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -35,8 +37,25 @@ int main(int argc, char** argv) {
     char magic[4];
     uint32_t n_cols, n_pages;
     uint64_t n_bytes;
-    if (fread(magic, 1, 4, f) != 4 || memcmp(magic, "PQGB", 4) || fread(&n_cols, 4, 1, f) != 1 ||
-        fread(&n_pages, 4, 1, f) != 1 || fread(&n_bytes, 8, 1, f) != 1)
+    if (fread(magic, 1, 4, f) != 4) return 2;
+#ifdef PQR_SANITIZE_ZSTD
+    if (!memcmp(magic, "PQGZ", 4)) {
+      uint64_t expect, n;
+      if (fread(&expect, 8, 1, f) != 1 || fread(&n, 8, 1, f) != 1) return 2;
+      uint8_t* src = malloc(n ? n : 1);
+      uint8_t* dst = malloc(expect ? expect : 1);
+      if (fread(src, 1, n, f) != n) return 2;
+      fclose(f);
+      int64_t produced = 0;
+      const int zrc = pqr_zstd_decompress(src, (int64_t)n, dst, (int64_t)expect, &produced);
+      printf("%s rc=%d\n", argv[a], zrc);
+      free(src);
+      free(dst);
+      continue;
+    }
+#endif
+    if (memcmp(magic, "PQGB", 4) || fread(&n_cols, 4, 1, f) != 1 || fread(&n_pages, 4, 1, f) != 1 ||
+        fread(&n_bytes, 8, 1, f) != 1)
       return 2;
     pqg_column_desc* cols = calloc(n_cols + 1, sizeof(*cols));
     pqg_page_desc* pages = calloc(n_pages + 1, sizeof(*pages));

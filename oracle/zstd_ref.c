@@ -180,6 +180,11 @@ static int huf_build(HufTab* H, const uint8_t* w, int nsym) {
   W[nsym] = (uint8_t)(highbit(left) + 1);
   nsym++;
   if (max_bits > 11) return -1;
+  /* a complete tree has (at least) two codes of the full length; libzstd (HUF_readStats) refuses
+   * weights without two symbols of weight 1 */
+  int ones = 0;
+  for (int s = 0; s < nsym; s++) ones += W[s] == 1;
+  if (ones < 2) return -1;
   H->max_bits = max_bits;
   /* canonical prefix codes: ranks by weight, weight 1 (longest codes) first */
   uint32_t next = 0;
@@ -288,8 +293,7 @@ static int seq_table(FseTab* T, int* have, int mode, const uint8_t* p, int64_t n
   }
 }
 
-static int block_compressed(ZState* Z, const uint8_t* p, int64_t n, int64_t window_bytes) {
-  (void)window_bytes;
+static int block_compressed(ZState* Z, const uint8_t* p, int64_t n) {
   if (n < 1) return -1;
   /* literals section */
   const int lt = p[0] & 3, sf = (p[0] >> 2) & 3;
@@ -328,7 +332,7 @@ static int block_compressed(ZState* Z, const uint8_t* p, int64_t n, int64_t wind
     if (sf == 0) {
       if (huf_stream(&Z->huf, c, cn, Z->lit, regen)) return -1;
     } else {
-      if (cn < 6) return -1;
+      if (cn < 6 || regen < 6) return -1;  /* (libzstd: 4 streams hold at least 6 literals) */
       const int64_t s1 = c[0] | (c[1] << 8), s2 = c[2] | (c[3] << 8), s3 = c[4] | (c[5] << 8);
       const int64_t s4 = cn - 6 - s1 - s2 - s3;
       if (s4 < 0) return -1;
@@ -345,14 +349,13 @@ static int block_compressed(ZState* Z, const uint8_t* p, int64_t n, int64_t wind
   /* sequences section */
   if (q >= n) return -1;
   int64_t nseq = p[q];
-  if (nseq == 0) {
-    q += 1;
-    for (int64_t i = 0; i < regen; i++) out_byte(Z, Z->lit[i]);
-    return q == n ? 0 : -1;
-  }
   if (nseq < 128) { q += 1; }
   else if (nseq < 255) { if (q + 2 > n) return -1; nseq = ((nseq - 128) << 8) + p[q + 1]; q += 2; }
   else { if (q + 3 > n) return -1; nseq = p[q + 1] + ((int64_t)p[q + 2] << 8) + 0x7F00; q += 3; }
+  if (nseq == 0) {  /* in the 1-byte form or (as libzstd reads it) the 2-byte one: the section ends here */
+    for (int64_t i = 0; i < regen; i++) out_byte(Z, Z->lit[i]);
+    return q == n ? 0 : -1;
+  }
   if (q >= n) return -1;
   const uint8_t modes = p[q++];
   if (modes & 3) return -1;
@@ -447,7 +450,7 @@ static int zstd_frames(ZState* Z, const uint8_t* src, int64_t n, uint8_t* dst, i
     const uint8_t fhd = src[p++];
     const int fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, checksum = (fhd >> 2) & 1, did_flag = fhd & 3;
     if (fhd & 8) return ZR_CORRUPT;  /* reserved bit */
-    int64_t window = 0;  /* Window_Size (not needed to decode a whole frame in memory) */
+    int64_t window = 0;  /* Window_Size: bounds the compressed blocks (Block_Maximum_Size) */
     if (!single) {
       if (p >= n) return ZR_CORRUPT;
       const uint8_t wd = src[p++];
@@ -490,8 +493,11 @@ static int zstd_frames(ZState* Z, const uint8_t* src, int64_t n, uint8_t* dst, i
         if (type == 0) {
           for (int64_t k = 0; k < bs; k++) out_byte(Z, src[p + k]);
         } else {
+          /* Block_Maximum_Size = min(Window_Size, 128 KiB), RFC 8878 3.1.1.2.3. Compressed blocks
+           * only: libzstd lets an oversized Raw (or RLE) block through, and so does this. */
+          if (bs > (window < 131072 ? window : 131072)) return ZR_CORRUPT;
           const int64_t before = Z->pos;
-          if (block_compressed(Z, src + p, bs, window)) return ZR_CORRUPT;
+          if (block_compressed(Z, src + p, bs)) return ZR_CORRUPT;
           if (Z->pos - before > 131072) return ZR_CORRUPT;
         }
         p += bs;

@@ -204,6 +204,7 @@ struct pqg_ctx {
   bool dict_fused = true;   // PQG_DISPATCH_DICT_FUSED
   bool null_hints = true;   // PQG_DISPATCH_NULL_HINTS
   uint32_t gz_prepass_min = pqg::GZ_PREPASS_MIN;  // PQG_DISPATCH_GZIP_PREPASS_MIN
+  bool zstd_prepass = true;  // PQG_DISPATCH_ZSTD_PREPASS
   RouterCache router;  // pqg_router_read_page
   // pqg_filter_run: per-tile counts, and the device image of the filter uploaded last (by its serial)
   DevBuf filter_scratch, filter_image;
@@ -312,6 +313,10 @@ int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value) {
     case PQG_DISPATCH_TAKE_STAGED:
       if (value != 0 && value != 1) return PQG_ERR_INVALID_ARG;
       ctx->take_staged = value != 0;
+      return PQG_OK;
+    case PQG_DISPATCH_ZSTD_PREPASS:
+      if (value != 0 && value != 1) return PQG_ERR_INVALID_ARG;
+      ctx->zstd_prepass = value != 0;
       return PQG_OK;
     default: return PQG_ERR_INVALID_ARG;
   }
@@ -1799,9 +1804,10 @@ int pqg_zstd_decompress(pqg_ctx* ctx, const uint8_t* d_src, uint64_t src_bytes, 
   }
   // sequence pre-pass scratch: dst_bytes / 5 + 1 eight-byte records (a job's records start at its
   // dst_offset / 5) and one mode word per job; without it every job takes the inline decoder
+  // (PQG_DISPATCH_ZSTD_PREPASS 0 asks for exactly that)
   uint64_t* seqs = nullptr;
   int32_t* mode = nullptr;
-  {
+  if (ctx->zstd_prepass) {
     const size_t need_s = 8u * (size_t)(dst_bytes / 5u + 2u), need_m = 4u * (size_t)n_jobs;
     if (ctx->zstd_seqs.cap < need_s || ctx->zstd_mode.cap < need_m) {
       if (hipStreamSynchronize(ctx->stream) != hipSuccess) return PQG_ERR_HIP;

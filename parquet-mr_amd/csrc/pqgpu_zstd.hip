@@ -358,16 +358,18 @@ __device__ bool zseq_table(ZWaveLds& L, uint32_t* tab, int* tlog, bool& have, in
 
 // Huffman decoding table from weights L.ph.t.wts[0, nsym) (+ the implied last weight), RFC 8878 §4.2.1.
 __device__ int zhuf_build(ZWaveLds& L, int nsym) {
-  uint32_t total = 0;
+  uint32_t total = 0, ones = 0;
   for (int s = 0; s < nsym; s++) {
     const uint32_t w = L.ph.t.wts[s];
     if (w > 11) return -1;
     if (w) total += 1u << (w - 1);
+    ones += w == 1u;
   }
   if (!total) return -1;
   const int max_bits = zhigh(total) + 1;
   const uint32_t left = (1u << max_bits) - total;
   if (max_bits > 11 || (left & (left - 1u))) return -1;
+  if (ones + (left == 1u) < 2u) return -1;  // libzstd (HUF_readStats): at least two symbols of weight 1
   if (lane_id() == 0) L.ph.t.wts[nsym] = (uint8_t)(zhigh(left) + 1);
   wave_sync();
   nsym++;
@@ -781,7 +783,7 @@ __device__ __forceinline__ int zblock(ZWaveLds& L, ZOut& O, rsrc_t rs, uint32_t 
     uint32_t sb[4] = {c, 0, 0, 0}, sn[4] = {cend - c, 0, 0, 0}, cnt[4] = {regen, 0, 0, 0}, dst0[4] = {0, 0, 0, 0};
     int ns = 1;
     if (sf != 0) {
-      if (cend - c < 6) return PQG_ERR_CORRUPT;
+      if (cend - c < 6 || regen < 6) return PQG_ERR_CORRUPT;  // (libzstd: 4 streams hold at least 6 literals)
       const uint32_t s1 = zbyte(rs, c) | (zbyte(rs, c + 1) << 8), s2 = zbyte(rs, c + 2) | (zbyte(rs, c + 3) << 8),
                      s3 = zbyte(rs, c + 4) | (zbyte(rs, c + 5) << 8);
       const uint32_t tot = cend - c - 6;
@@ -838,14 +840,13 @@ __device__ __forceinline__ int zblock(ZWaveLds& L, ZOut& O, rsrc_t rs, uint32_t 
   // ---- sequences
   if (p >= lim) return PQG_ERR_CORRUPT;
   uint32_t nseq = zbyte(rs, p);
-  if (nseq == 0) {
-    p += 1;
-    zcopy_lits(O, L, lit_kind, rs, lit_src, litbuf, regen);
-    return p == lim ? 0 : PQG_ERR_CORRUPT;
-  }
   if (nseq < 128) { p += 1; }
   else if (nseq < 255) { nseq = ((nseq - 128) << 8) + zbyte(rs, p + 1); p += 2; }
   else { nseq = zbyte(rs, p + 1) + (zbyte(rs, p + 2) << 8) + 0x7F00u; p += 3; }
+  if (nseq == 0) {  // in the 1-byte form or (as libzstd reads it) the 2-byte one: the section ends here
+    zcopy_lits(O, L, lit_kind, rs, lit_src, litbuf, regen);
+    return p == lim ? 0 : PQG_ERR_CORRUPT;
+  }
   if (p >= lim) return PQG_ERR_CORRUPT;
   if (rec) {  // replay: k_zstd_seq decoded (and checked) this block's sequences
     ZD_T(t_rep);
@@ -1192,13 +1193,13 @@ __device__ bool zq_block_seqs(ZqLds& L, ZqLane& T, rsrc_t rs, uint32_t q, uint32
                               uint32_t cap ZQD_ARG) {
   if (q >= lim) return false;
   uint32_t nseq = zbyte(rs, q);
-  if (nseq == 0) {
-    outp += regen;
-    return q + 1u == lim;
-  }
   if (nseq < 128) { q += 1; }
   else if (nseq < 255) { nseq = ((nseq - 128) << 8) + zbyte(rs, q + 1); q += 2; }
   else { nseq = zbyte(rs, q + 1) + (zbyte(rs, q + 2) << 8) + 0x7F00u; q += 3; }
+  if (nseq == 0) {
+    outp += regen;
+    return q == lim;
+  }
   if (q >= lim) return false;
   const uint32_t modes = zbyte(rs, q++);
   if (modes & 3u) return false;
@@ -1379,7 +1380,11 @@ __device__ int32_t zq_job(ZqLds& L, ZqLane& T, rsrc_t rs, const pqg_snappy_job& 
     const uint32_t fhd = zbyte(rs, p++);
     const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1u, checksum = (fhd >> 2) & 1u, did_flag = fhd & 3u;
     if (fhd & 8u) return ZQ_INLINE;
-    if (!single) p++;
+    uint64_t window = 0;  // Window_Size (zstd_job)
+    if (!single) {
+      const uint32_t wd = zbyte(rs, p++);
+      window = (1ull << (10u + (wd >> 3))) / 8u * (wd & 7u) + (1ull << (10u + (wd >> 3)));
+    }
     const uint32_t did_sz = did_flag == 3 ? 4u : did_flag;
     uint32_t did = 0;
     for (uint32_t i = 0; i < did_sz; i++) did |= zbyte(rs, p + i) << (8 * i);
@@ -1391,6 +1396,8 @@ __device__ int32_t zq_job(ZqLds& L, ZqLane& T, rsrc_t rs, const pqg_snappy_job& 
     for (uint32_t i = 0; i < fcs_sz; i++) fcs |= (uint64_t)zbyte(rs, p + i) << (8 * i);
     if (fcs_sz == 2) fcs += 256;
     p += fcs_sz;
+    if (single) window = fcs;
+    const uint32_t bmax = window < ZS_LIT_MAX ? (uint32_t)window : ZS_LIT_MAX;
     const uint32_t frame0 = outp;
     uint32_t rep[3] = {1, 4, 8};
     bool have_tab[3] = {false, false, false};
@@ -1412,7 +1419,7 @@ __device__ int32_t zq_job(ZqLds& L, ZqLane& T, rsrc_t rs, const pqg_snappy_job& 
         outp += bs;
         p += bs;
       } else {
-        if (p + bs > end || bs < 1) return ZQ_INLINE;
+        if (p + bs > end || bs < 1 || bs > bmax) return ZQ_INLINE;
         const uint32_t lim = p + bs, before = outp;
         // literals section header (the literals themselves are k_zstd's)
         const uint32_t b0 = zbyte(rs, p);
@@ -1547,7 +1554,14 @@ __device__ __forceinline__ void zstd_job(ZWaveLds& L, const uint8_t* __restrict_
     const uint32_t fhd = zbyte(rs, p++);
     const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1u, checksum = (fhd >> 2) & 1u, did_flag = fhd & 3u;
     if (fhd & 8u) { code = PQG_ERR_CORRUPT; break; }
-    if (!single) p++;  // Window_Descriptor: the whole frame is decoded in place
+    // Window_Size: the whole frame is decoded in place, so it only bounds the compressed blocks.
+    // Block_Maximum_Size = min(Window_Size, 128 KiB), RFC 8878 3.1.1.2.3; a Single_Segment frame's
+    // Window_Size is its Frame_Content_Size.
+    uint64_t window = 0;
+    if (!single) {
+      const uint32_t wd = zbyte(rs, p++);
+      window = (1ull << (10u + (wd >> 3))) / 8u * (wd & 7u) + (1ull << (10u + (wd >> 3)));
+    }
     const uint32_t did_sz = did_flag == 3 ? 4u : did_flag;
     uint32_t did = 0;
     for (uint32_t i = 0; i < did_sz; i++) did |= zbyte(rs, p + i) << (8 * i);
@@ -1559,6 +1573,8 @@ __device__ __forceinline__ void zstd_job(ZWaveLds& L, const uint8_t* __restrict_
     for (uint32_t i = 0; i < fcs_sz; i++) fcs |= (uint64_t)zbyte(rs, p + i) << (8 * i);
     if (fcs_sz == 2) fcs += 256;
     p += fcs_sz;
+    if (single) window = fcs;
+    const uint32_t bmax = window < ZS_LIT_MAX ? (uint32_t)window : ZS_LIT_MAX;
     O.frame0 = O.pos;
     uint32_t rep[3] = {1, 4, 8};
     bool have_huf = false, have_tab[3] = {false, false, false};
@@ -1580,7 +1596,8 @@ __device__ __forceinline__ void zstd_job(ZWaveLds& L, const uint8_t* __restrict_
         zcopy_lits(O, L, 0, rs, p, litbuf, bs);
         p += bs;
       } else {
-        if (p + bs > n) { code = PQG_ERR_CORRUPT; break; }
+        // (compressed blocks only: libzstd lets an oversized Raw or RLE block through, and so does this)
+        if (p + bs > n || bs > bmax) { code = PQG_ERR_CORRUPT; break; }
         const uint32_t before = O.pos;
         code = zblock(L, O, rs, p, bs, litbuf, have_huf, huf_bits, have_tab, tlog, rep, rec, rc);
         if (!code && O.pos - before > ZS_LIT_MAX) code = PQG_ERR_CORRUPT;

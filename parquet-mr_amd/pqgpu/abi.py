@@ -222,6 +222,7 @@ DISPATCH_DICT_DIRECT = 2
 DISPATCH_GZIP_PREPASS_MIN = 3  # pqg_gzip_decompress: smallest page (output bytes) for the token pre-pass
 DISPATCH_DICT_FUSED = 4  # dictionary pages: 1 = walk + expansion in one launch, 0 = two launches
 DISPATCH_TAKE_STAGED = 6  # pqg_take: 1 = kept elements staged in LDS and stored as aligned full-wave runs, 0 = one store per kept lane
+DISPATCH_ZSTD_PREPASS = 7  # pqg_zstd_decompress: 1 = sequence pre-pass + replay, 0 = every page through the inline decoder
 DISPATCH_NULL_HINTS = 5  # V2 nullable columns: 1 = value kernels from the header null counts (verified), 0 = levels first
 
 

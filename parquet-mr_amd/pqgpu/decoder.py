@@ -240,7 +240,9 @@ class Decoder:
 
     def zstd_decompress(self, frames, sizes):
         """Raw Zstandard frames (host bytes) -> device tensor of the concatenated outputs (each at a
-        16-byte aligned offset) + the offsets, decompressed by pqg_zstd_decompress.
+        16-byte aligned offset, at least 16 bytes apart; the tensor starts out as the decoder's poison
+        byte, or zeros) + the
+        offsets, decompressed by pqg_zstd_decompress.
         Returns (out_tensor, offsets, status_codes, status)."""
         src, soff, pos = [], [], 0
         for b in frames:
@@ -253,7 +255,7 @@ class Decoder:
         table["src_offset"], table["dst_offset"] = soff, doff[:-1]
         table["src_size"], table["dst_size"] = [len(b) for b in frames], sizes
         d_src = torch.from_numpy(np.frombuffer(b"".join(src) + bytes(16), dtype=np.uint8).copy()).to(self.device)
-        d_dst = torch.zeros(int(doff[-1]) + 16, dtype=torch.uint8, device=self.device)
+        d_dst = torch.full((int(doff[-1]) + 16,), int(self.poison or 0), dtype=torch.uint8, device=self.device)
         d_jobs = torch.from_numpy(table.view(np.uint8).copy()).to(self.device)
         d_status = torch.full((max(len(frames), 1),), -1, dtype=torch.int32, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()

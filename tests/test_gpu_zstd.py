@@ -32,14 +32,26 @@ def _oracle(frame, size):
         return int(str(e).split("error ")[1].split()[0].rstrip(")")), None
 
 
+def _run_both(decoder, frames, sizes):
+    """_run with PQG_DISPATCH_ZSTD_PREPASS 1 (default: sequence pre-pass + replay), then 0 (every page
+    through the inline decoder, otherwise only the pre-pass's fallback): yields (mode, outputs, status)."""
+    for prepass in (1, 0):
+        decoder.set_dispatch(abi.DISPATCH_ZSTD_PREPASS, prepass)
+        try:
+            got, status = _run(decoder, frames, sizes)
+        finally:
+            decoder.set_dispatch(abi.DISPATCH_ZSTD_PREPASS, 1)
+        yield prepass, got, status
+
+
 def test_golden_frames(decoder):
     names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "*.zst")))
     raws = [open(os.path.join(GOLD, n + ".raw"), "rb").read() for n in names]
     comps = [open(os.path.join(GOLD, n + ".zst"), "rb").read() for n in names]
-    got, status = _run(decoder, comps, [len(r) for r in raws])
-    assert list(status) == [0] * len(names)
-    for n, g, r in zip(names, got, raws):
-        assert g == r, n
+    for prepass, got, status in _run_both(decoder, comps, [len(r) for r in raws]):
+        assert list(status) == [0] * len(names), prepass
+        for n, g, r in zip(names, got, raws):
+            assert g == r, (n, prepass)
 
 
 @pytest.mark.parametrize("level", [1, 3, 9, 19, -5])
@@ -65,11 +77,11 @@ def test_libzstd_frames(decoder, level):
             raws.append(b"".join(words[int(j)] for j in rng.integers(0, 50, size=n // 6 + 1))[:n])
     codec = pa.Codec("zstd", compression_level=level)
     comps = [codec.compress(r, asbytes=True) for r in raws]
-    got, status = _run(decoder, comps, [len(r) for r in raws])
-    bad = [(i, int(status[i]), len(raws[i]), len(comps[i]), i % 5) for i in range(len(raws)) if status[i]]
-    assert not bad, bad
-    for i, (g, r) in enumerate(zip(got, raws)):
-        assert g == r, (i, len(r))
+    for prepass, got, status in _run_both(decoder, comps, [len(r) for r in raws]):
+        bad = [(i, int(status[i]), len(raws[i]), len(comps[i]), i % 5) for i in range(len(raws)) if status[i]]
+        assert not bad, (prepass, bad)
+        for i, (g, r) in enumerate(zip(got, raws)):
+            assert g == r, (i, len(r), prepass)
 
 
 def test_header_size_and_concatenated_frames(decoder):
