@@ -37,7 +37,8 @@
  * ABI 6 (this version): the rows a selection bitmap keeps, gathered into compact columns on the
  * device (pqg_take; PQG_DISPATCH_TAKE_STAGED). Added to ABI 6 without a change to what it had:
  * record filters on dictionary-id columns (pqg_filter_dictionary, pqg_filter_run_dict,
- * PQG_FILTER_DICT_LDS_BYTES) and pqg_decode_dictionary.
+ * PQG_FILTER_DICT_LDS_BYTES) and pqg_decode_dictionary; record selection on repeated columns
+ * (pqg_take_record_column, pqg_take_record_counts, pqg_take_records).
  * ABI 5: record-level filter2 predicates over decoded columns (pqg_filter_create /
  * pqg_filter_program / pqg_filter_destroy on the host, pqg_filter_run on the device).
  * ABI 4: pqg_page_desc carries the V2 header's num_nulls
@@ -876,12 +877,76 @@ typedef struct pqg_take_result {
  * misaligned or missing pointer the column needs (values with n_values > 0, offsets and bytes of a
  * BYTE_ARRAY column, out_values with a capacity, out_def_levels of a nullable column with
  * out_rows_capacity > 0), a required column with n_values < n_rows; PQG_ERR_UNSUPPORTED: more than
- * PQG_TAKE_MAX_COLUMNS columns. Repeated columns are out of scope (no repetition levels here).
+ * PQG_TAKE_MAX_COLUMNS columns. Repeated columns are out of scope (no repetition levels here;
+ * pqg_take_records below takes them).
  * Launches, none of which waits on another workgroup and whose number does not depend on n_cols: per
  * (column, tile) counts, their scans, with BYTE_ARRAY columns the kept bytes per tile and their scan,
  * the verdicts, the gather (one wave per column and tile of PQG_FILTER_TILE_ROWS rows). */
 int pqg_take(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_column* cols, int n_cols,
              uint64_t out_rows_capacity, pqg_take_counts* d_counts, pqg_take_result* d_result);
+
+/* ---- record selection on repeated columns (an addition to ABI 6) ----------------------------------
+ * pqg_take for schemas with lists: the bitmap names RECORDS, and every leaf loses the same records,
+ * nested leaves included. That is what the reference does: RecordReaderImplementation.read drops a
+ * whole record when shouldSkipCurrentRecord says so (RecordReaderImplementation.java:440-449,
+ * FilteringRecordMaterializer), and SynchronizingColumnReader skips the rows outside the RowRanges;
+ * both act on records. Its record filter cannot name a repeated column (SchemaCompatibilityValidator:
+ * "FilterPredicates do not currently support repeated columns"), but the filter's result applies to all
+ * columns of the record: the normal case is a filter on flat columns and a take on every column.
+ *
+ * A repeated leaf is a stripe of SLOTS (one repetition byte and one definition byte per slot, dense
+ * values for the slots with def == max_def), as pqg_decode writes it. Record i of a column is the run of
+ * slots from the i-th slot with rep == 0 up to the next such slot. */
+typedef struct pqg_take_record_column {
+  pqg_take_column col;         /* as for pqg_take; def_levels / out_def_levels hold one byte per SLOT */
+  int32_t max_rep;             /* 0: a flat column (rep_levels NULL, n_slots == n_rows, out_rep_levels unused) */
+  int32_t reserved;            /* 0 */
+  const uint8_t* rep_levels;   /* device, one byte per slot, as pqg_decode wrote them */
+  uint64_t n_slots;
+  uint8_t* out_rep_levels;     /* device, one byte per kept slot */
+  uint64_t out_slots_capacity; /* bounds out_rep_levels and out_def_levels of this column */
+} pqg_take_record_column;
+
+/* Per column, device-resident. */
+typedef struct pqg_take_record_counts {
+  uint64_t n_records; /* record starts found in the column, whatever n_rows is (a flat column: n_rows;
+                         a missing column: 0) */
+  uint64_t n_slots;   /* kept slots (a flat column: kept rows), whatever the capacities are */
+  uint64_t n_values;  /* dense values of the kept slots, whatever the capacities are */
+  uint64_t n_bytes;   /* BYTE_ARRAY: bytes of those values; 0 otherwise */
+} pqg_take_record_counts;
+
+/* Keep the records of [0, n_rows) whose bit is set in d_bitmap (the layout of pqg_take; bits past n_rows
+ * in the last word are ignored). A slot is kept iff its record's bit is set. Per column, for the kept
+ * slots in slot order: out_rep_levels and out_def_levels are copied byte for byte (repetition values
+ * above 0 are not interpreted); out_values holds the dense values of the kept slots with def == max_def;
+ * BYTE_ARRAY columns get offsets from 0, bytes without gaps and the closing offset always written, as
+ * for pqg_take; a missing column (max_def > 0, def_levels == NULL) produces only zero counts; dictionary
+ * ids travel as 4-byte elements. A column with max_rep == 0 gives outputs byte-identical to pqg_take on
+ * `col` (out_rows_capacity bounds its level bytes, as there). d_result->n_rows is the number of kept
+ * records. The outputs are valid inputs to pqg_take_records again and to pqg_assemble.
+ * d_result->error = PQG_ERR_INVALID_ARG with error_column the lowest bad column when: slot 0 of a
+ * repeated column has rep != 0; the column's record starts differ in number from n_rows; its slots with
+ * def == max_def differ in number from n_values; the kept records exceed out_rows_capacity (against
+ * every column); the kept slots exceed out_slots_capacity, the kept values out_values_capacity, the kept
+ * bytes out_binary_capacity. The outputs are then undefined, but no load leaves [0, n_slots),
+ * [0, n_values) or the bitmap's ceil(n_rows / 64) words (a slot whose record index is -1 or >= n_rows is
+ * simply not kept), and no store passes a stated capacity.
+ * Refused before any launch, PQG_ERR_INVALID_ARG: everything pqg_take refuses for `col`; max_rep outside
+ * 0..254 or non-zero `reserved`; max_rep > 0 with max_def == 0 (a repeated node always adds a definition
+ * level), without rep_levels (a missing column is exempt), or with out_slots_capacity > 0 but no
+ * out_rep_levels or no out_def_levels; n_slots < n_rows on a column that is not missing; max_rep == 0
+ * with rep_levels or with n_slots != n_rows. PQG_ERR_UNSUPPORTED: more than PQG_TAKE_MAX_COLUMNS
+ * columns. n_rows == 0 and n_cols == 0 are valid.
+ * Launches, none of which waits on another workgroup and whose number does not depend on n_cols: the
+ * record starts per (repeated column, tile of PQG_FILTER_TILE_ROWS slots), their scan, the expansion of
+ * the record bitmap into one slot bitmap per repeated column; then the launches of pqg_take with every
+ * column on its own bitmap (a flat column on d_bitmap, a repeated one on its slot bitmap, its repetition
+ * bytes gathered as a required 1-byte column on the same bitmap). PQG_DISPATCH_TAKE_STAGED applies.
+ * Not covered: a record filter on a repeated column (the reference refuses it) and contains(). */
+int pqg_take_records(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_record_column* cols,
+                     int n_cols, uint64_t out_rows_capacity, pqg_take_record_counts* d_counts,
+                     pqg_take_result* d_result);
 
 /* Human-readable name of an error code. */
 const char* pqg_error_name(int code);

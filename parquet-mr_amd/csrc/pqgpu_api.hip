@@ -221,6 +221,8 @@ struct pqg_ctx {
   // pqg_take: per-tile counts; the column table on the device and the pinned slots it is copied from
   // (a slot is reused once the copy out of it has run: its event)
   static constexpr int TAKE_SLOTS = 4;
+  // one slot holds the table of either call (pqg_take: TakeColDev, pqg_take_records: TakeRecDev)
+  static constexpr size_t TAKE_SLOT_BYTES = sizeof(pqg::TakeRecDev) * pqg::TAKE_REC_MAX_RECORDS;
   DevBuf take_scratch, take_cols;
   PinnedBuf take_pin;
   hipEvent_t take_ev[TAKE_SLOTS] = {};
@@ -1664,7 +1666,8 @@ int pqg_take(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_
     any_binary |= tab[i].kind == pqg::TAKE_BINARY;
   }
   if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
-  constexpr size_t slot_bytes = sizeof(tab);
+  constexpr size_t slot_bytes = pqg_ctx::TAKE_SLOT_BYTES;
+  static_assert(sizeof(tab) <= slot_bytes, "a pinned slot holds the table");
   if (ctx->take_scratch.ensure(8 * (size_t)pqg::take_scratch_words(n_rows, (uint32_t)n_cols)) != hipSuccess ||
       ctx->take_cols.ensure(slot_bytes) != hipSuccess || ctx->take_pin.ensure(slot_bytes * pqg_ctx::TAKE_SLOTS) != hipSuccess)
     return PQG_ERR_HIP;
@@ -1686,6 +1689,45 @@ int pqg_take(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_
   const hipError_t e = pqg::launch_take(ctx->stream, d_bitmap, n_rows, (const pqg::TakeColDev*)ctx->take_cols.p, (uint32_t)n_cols,
                                         any_nullable, any_binary, out_rows_capacity, (uint64_t*)ctx->take_scratch.p, d_counts,
                                         d_result, ctx->take_staged);
+  return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+// ---- record selection on repeated columns --------------------------------------------------------
+static_assert(sizeof(pqg_take_record_column) == 128 && sizeof(pqg_take_record_counts) == 32, "take_records ABI layout");
+
+int pqg_take_records(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_record_column* cols,
+                     int n_cols, uint64_t out_rows_capacity, pqg_take_record_counts* d_counts,
+                     pqg_take_result* d_result) {
+  pqg::TakeRecDev tab[pqg::TAKE_REC_MAX_RECORDS];
+  pqg::TakeRecPlan plan;
+  const int rc = pqg::take_records_validate(ctx != nullptr, d_bitmap, n_rows, cols, n_cols, out_rows_capacity, d_counts,
+                                            d_result, tab, &plan);
+  if (rc != PQG_OK) return rc;
+  if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
+  constexpr size_t slot_bytes = pqg_ctx::TAKE_SLOT_BYTES;
+  static_assert(sizeof(tab) <= slot_bytes, "a pinned slot holds the table");
+  const uint64_t words = pqg::take_records_scratch_words(plan.max_rows, (uint32_t)n_cols, plan.slot_words);
+  if (ctx->take_scratch.ensure(8 * (size_t)words) != hipSuccess || ctx->take_cols.ensure(slot_bytes) != hipSuccess ||
+      ctx->take_pin.ensure(slot_bytes * pqg_ctx::TAKE_SLOTS) != hipSuccess)
+    return PQG_ERR_HIP;
+  if (plan.n_records) {  // the table goes up through the pinned slots of pqg_take
+    const uint32_t slot = ctx->take_seq++ % pqg_ctx::TAKE_SLOTS;
+    hipEvent_t& ev = ctx->take_ev[slot];
+    if (!ev) {
+      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return PQG_ERR_HIP;
+    } else if (hipEventSynchronize(ev) != hipSuccess) {
+      return PQG_ERR_HIP;
+    }
+    void* pin = (uint8_t*)ctx->take_pin.p + slot * slot_bytes;
+    std::memcpy(pin, tab, sizeof(pqg::TakeRecDev) * (size_t)plan.n_records);
+    if (hipMemcpyAsync(ctx->take_cols.p, pin, sizeof(pqg::TakeRecDev) * (size_t)plan.n_records, hipMemcpyHostToDevice,
+                       ctx->stream) != hipSuccess ||
+        hipEventRecord(ev, ctx->stream) != hipSuccess)
+      return PQG_ERR_HIP;
+  }
+  const hipError_t e = pqg::launch_take_records(ctx->stream, d_bitmap, n_rows, (const pqg::TakeRecDev*)ctx->take_cols.p,
+                                                (uint32_t)n_cols, plan, out_rows_capacity, (uint64_t*)ctx->take_scratch.p,
+                                                d_counts, d_result, ctx->take_staged);
   return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
 }
 

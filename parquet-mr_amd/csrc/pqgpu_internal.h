@@ -166,12 +166,20 @@ hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_
 // pqgpu_take.hip: pqg_take. scratch (u64 words): keep[n_tiles], rank[n_cols][n_tiles], kept[n_cols][n_tiles],
 // bytes[n_cols][n_tiles] (per-tile counts, scanned in place), totals[1 + 3 n_cols]
 struct TakeColDev;
+struct TakeRecDev;
+struct TakeRecPlan;
 inline uint64_t take_scratch_words(uint64_t n_rows, uint32_t n_cols) {
   return (1 + 3 * (uint64_t)n_cols) * (filter_tiles(n_rows) + 1);
 }
 hipError_t launch_take(hipStream_t st, const uint64_t* bitmap, uint64_t n_rows, const TakeColDev* d_cols, uint32_t n_cols,
                        bool any_nullable, bool any_binary, uint64_t rows_capacity, uint64_t* scratch,
                        pqg_take_counts* counts, pqg_take_result* result, bool staged);
+// pqgpu_take.hip: pqg_take_records. d_recs: plan.n_records records whose own slot bitmaps lie at
+// slot_off inside the scratch (layout: see rec_scratch)
+uint64_t take_records_scratch_words(uint64_t max_rows, uint32_t n_cols, uint64_t slot_words);
+hipError_t launch_take_records(hipStream_t st, const uint64_t* bitmap, uint64_t n_rows, const TakeRecDev* d_recs,
+                               uint32_t n_cols, const TakeRecPlan& plan, uint64_t rows_capacity, uint64_t* scratch,
+                               pqg_take_record_counts* counts, pqg_take_result* result, bool staged);
 hipError_t launch_unpack_runs(hipStream_t st, int w, const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
                               const uint32_t* counts, const uint64_t* out_off, int32_t* out, int n_runs,
                               uint32_t max_count);

@@ -1,4 +1,5 @@
-// pqgpu_take.hip — the rows a selection bitmap keeps, gathered into compact columns (pqg_take).
+// pqgpu_take.hip — the rows a selection bitmap keeps, gathered into compact columns (pqg_take), and the
+// records it keeps of columns with repetition levels (pqg_take_records, second half of this file).
 //
 // Launches on the context's stream, none of which waits on another workgroup (every cross-tile
 // dependency is a launch boundary) and whose number does not depend on the number of columns (the
@@ -65,16 +66,10 @@ __device__ __forceinline__ uint64_t tile_word(const uint64_t* __restrict__ bitma
 }
 
 // ---- k_take_count ----------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * TT_WPB) void k_take_count(const uint64_t* __restrict__ bitmap, uint64_t n_rows,
-                                                            const TakeColDev* __restrict__ cols, uint32_t n_cols,
-                                                            uint64_t* __restrict__ scratch) {
-  const TakeScratch S = take_scratch(scratch, (n_rows + TT_ROWS - 1) / TT_ROWS, n_cols);
-  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
-  if (tile >= S.n_tiles) return;
-  const uint32_t ci = blockIdx.y;
-  const uint8_t* __restrict__ dl = ci < n_cols ? cols[ci].dl : nullptr;
-  if (ci != 0 && !dl) return;  // nothing to count: a required column's rank is the row, its kept values the kept rows
-  const uint32_t md = dl ? (uint32_t)cols[ci].max_def : 0;
+// One wave's counts over a tile: rows with dl == md, kept rows with dl == md (both 0 without dl), kept rows.
+__device__ __forceinline__ void take_count_tile(const uint64_t* __restrict__ bitmap, uint64_t n_rows, uint64_t tile,
+                                                const uint8_t* __restrict__ dl, uint32_t md, uint32_t& t_valid,
+                                                uint32_t& t_kept, uint32_t& t_keep) {
   const uint32_t lane = lane_id();
   const uint64_t row0 = tile * TT_ROWS;
   const uint8_t* __restrict__ bm = (const uint8_t*)bitmap;
@@ -102,11 +97,24 @@ __global__ __launch_bounds__(64 * TT_WPB) void k_take_count(const uint64_t* __re
       n_kept += (uint32_t)__popc(valid & keep);
     }
   }
-  uint32_t t_valid, t_kept, t_keep;
   (void)wave_excl_scan_u32(n_valid, &t_valid);
   (void)wave_excl_scan_u32(n_kept, &t_kept);
   (void)wave_excl_scan_u32(n_keep, &t_keep);
-  if (lane == 0) {
+}
+
+__global__ __launch_bounds__(64 * TT_WPB) void k_take_count(const uint64_t* __restrict__ bitmap, uint64_t n_rows,
+                                                            const TakeColDev* __restrict__ cols, uint32_t n_cols,
+                                                            uint64_t* __restrict__ scratch) {
+  const TakeScratch S = take_scratch(scratch, (n_rows + TT_ROWS - 1) / TT_ROWS, n_cols);
+  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
+  if (tile >= S.n_tiles) return;
+  const uint32_t ci = blockIdx.y;
+  const uint8_t* __restrict__ dl = ci < n_cols ? cols[ci].dl : nullptr;
+  if (ci != 0 && !dl) return;  // nothing to count: a required column's rank is the row, its kept values the kept rows
+  const uint32_t md = dl ? (uint32_t)cols[ci].max_def : 0;
+  uint32_t t_valid, t_kept, t_keep;
+  take_count_tile(bitmap, n_rows, tile, dl, md, t_valid, t_kept, t_keep);
+  if (lane_id() == 0) {
     if (ci == 0) gst(&S.keep[tile], (uint64_t)t_keep);
     if (dl) {
       gst(&S.rank[(uint64_t)ci * S.n_tiles + tile], (uint64_t)t_valid);
@@ -144,21 +152,15 @@ __device__ __forceinline__ void binary_span(const int64_t* __restrict__ off, uin
 }
 
 // ---- k_take_bytes ----------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * TT_WPB) void k_take_bytes(const uint64_t* __restrict__ bitmap, uint64_t n_rows,
-                                                            const TakeColDev* __restrict__ cols, uint32_t n_cols,
-                                                            uint64_t* __restrict__ scratch) {
-  const TakeScratch S = take_scratch(scratch, (n_rows + TT_ROWS - 1) / TT_ROWS, n_cols);
-  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
-  if (tile >= S.n_tiles) return;
-  const uint32_t ci = blockIdx.y;
-  if (cols[ci].kind != TAKE_BINARY) return;
-  const TakeColDev c = cols[ci];
+// The bytes of the values a tile keeps of BYTE_ARRAY column c (in lane 63), rank0 the tile's source rank.
+__device__ __forceinline__ uint64_t take_bytes_tile(const uint64_t* __restrict__ bitmap, uint64_t n_rows, uint64_t tile,
+                                                    const TakeColDev c, uint64_t rank0) {
   const uint32_t lane = lane_id();
   const uint64_t row0 = tile * TT_ROWS;
   const uint64_t my_word = tile_word(bitmap, n_rows, tile);
   const int64_t* __restrict__ off = (const int64_t*)c.values;
   const int64_t lo = c.n_values ? off[0] : 0, hi = c.n_values ? off[c.n_values] : 0;
-  uint64_t next = c.dl ? S.rank[(uint64_t)ci * S.n_tiles + tile] : row0;
+  uint64_t next = rank0;
   uint64_t sum = 0;
   constexpr uint32_t G = 8;  // steps whose loads are issued together
   for (uint32_t g = 0; g < TT_STEPS; g += G) {
@@ -188,8 +190,20 @@ __global__ __launch_bounds__(64 * TT_WPB) void k_take_bytes(const uint64_t* __re
       sum += len;
     }
   }
-  sum = wave_incl_scan_u64(sum);
-  if (lane == 63) gst(&S.bytes[(uint64_t)ci * S.n_tiles + tile], sum);
+  return wave_incl_scan_u64(sum);
+}
+
+__global__ __launch_bounds__(64 * TT_WPB) void k_take_bytes(const uint64_t* __restrict__ bitmap, uint64_t n_rows,
+                                                            const TakeColDev* __restrict__ cols, uint32_t n_cols,
+                                                            uint64_t* __restrict__ scratch) {
+  const TakeScratch S = take_scratch(scratch, (n_rows + TT_ROWS - 1) / TT_ROWS, n_cols);
+  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
+  if (tile >= S.n_tiles) return;
+  const uint32_t ci = blockIdx.y;
+  if (cols[ci].kind != TAKE_BINARY) return;
+  const TakeColDev c = cols[ci];
+  const uint64_t sum = take_bytes_tile(bitmap, n_rows, tile, c, c.dl ? S.rank[(uint64_t)ci * S.n_tiles + tile] : tile * TT_ROWS);
+  if (lane_id() == 63) gst(&S.bytes[(uint64_t)ci * S.n_tiles + tile], sum);
 }
 
 // ---- k_take_finish ---------------------------------------------------------------------------
@@ -533,6 +547,313 @@ hipError_t launch_take(hipStream_t st, const uint64_t* bitmap, uint64_t n_rows, 
     else
       hipLaunchKernelGGL(k_take_gather<false>, dim3(wgs, n_cols), dim3(64 * TT_WPB), 0, st, bitmap, n_rows, d_cols, n_cols,
                          rows_capacity, scratch);
+  }
+  return hipGetLastError();
+}
+
+// ==== record selection on repeated columns (pqg_take_records) ====================================
+// The record bitmap is expanded into one slot bitmap per repeated column, and then the take above runs
+// with every record of the table on its own bitmap and row count (TakeRecDev): a flat column on the
+// caller's bitmap, a repeated column on its slot bitmap, its repetition bytes as a required 1-byte
+// column on the same slot bitmap. The gathers (TakeWalk, OutRing, gather_*) are the ones above.
+//   k_rec_count    per (repeated column, tile of slots): slots with rep == 0; tile 0 also the verdict
+//                  on slot 0
+//   k_rtake_scan   those counts: each tile's first record index, the column's record starts
+//   k_rec_expand   per (repeated column, tile): 64 steps of 64 slots, lane = slot: the slot's record
+//                  is the tile's base + the starts up to and including it - 1, its keep bit the
+//                  record's bit; lane k keeps the word of step k and the tile's words leave as one
+//                  512-byte store
+//   k_rtake_count / k_rtake_scan / k_rtake_bytes / k_rtake_scan / k_rtake_finish / k_rtake_gather
+// scratch (u64 words), C = n_cols, T = tiles of the largest record: five arrays of [C + 1][T] per-tile
+// counts scanned in place (kept rows, rank, kept values, bytes, record starts; row C of the first is
+// the caller's bitmap itself: the kept records), their totals [5][C + 1], the slot-0 flags [C], the
+// slot bitmaps (whole tiles per repeated column).
+enum : uint32_t { RA_KEEP = 0, RA_RANK = 1, RA_KEPT = 2, RA_BYTES = 3, RA_RECS = 4, RA_ARRAYS = 5 };
+
+struct RecScratch {
+  uint64_t *arr, *totals, *flags, *slots;
+  uint64_t n_tiles;
+  uint32_t n_cols;
+  __host__ __device__ uint64_t* tiles(uint32_t which, uint32_t ci) const {
+    return arr + ((uint64_t)which * (n_cols + 1) + ci) * n_tiles;
+  }
+  __host__ __device__ uint64_t* total(uint32_t which, uint32_t ci) const { return totals + which * (n_cols + 1) + ci; }
+};
+__host__ __device__ inline RecScratch rec_scratch(uint64_t* s, uint64_t n_tiles, uint32_t n_cols) {
+  RecScratch r;
+  r.n_tiles = n_tiles;
+  r.n_cols = n_cols;
+  r.arr = s;
+  r.totals = r.arr + (uint64_t)RA_ARRAYS * (n_cols + 1) * n_tiles;
+  r.flags = r.totals + RA_ARRAYS * (n_cols + 1);
+  r.slots = r.flags + n_cols;
+  return r;
+}
+uint64_t take_records_scratch_words(uint64_t max_rows, uint32_t n_cols, uint64_t slot_words) {
+  return (uint64_t)RA_ARRAYS * (n_cols + 1) * (filter_tiles(max_rows) + 1) + n_cols + slot_words;
+}
+
+__device__ __forceinline__ const uint64_t* rec_bitmap(const TakeRecDev& r, const RecScratch& S) {
+  return r.own_bitmap ? S.slots + r.slot_off : r.bitmap;
+}
+
+// ---- k_rec_count -----------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * TT_WPB) void k_rec_count(const TakeRecDev* __restrict__ recs, uint32_t n_cols,
+                                                           uint64_t n_tiles, uint64_t* __restrict__ scratch) {
+  const RecScratch S = rec_scratch(scratch, n_tiles, n_cols);
+  const uint32_t ci = blockIdx.y;
+  const uint8_t* __restrict__ rl = recs[ci].rl;
+  if (!rl) return;
+  const uint64_t n = recs[ci].n;
+  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
+  if (tile * TT_ROWS >= n) return;
+  const uint32_t lane = lane_id();
+  const uint64_t row0 = tile * TT_ROWS;
+  const bool words = ((uintptr_t)rl & 3u) == 0;
+  uint32_t starts = 0;
+  // a lane takes 4 slots at a time: their repetition bytes are one dword
+#pragma unroll 4
+  for (uint32_t k = 0; k < TT_ROWS / 256; k++) {
+    const uint64_t r = row0 + 4ull * (k * 64u + lane);
+    if (r >= n) continue;
+    if (words && r + 4 <= n) {
+      const uint32_t w = *(const uint32_t*)(rl + r);
+      starts += ((w & 0xFFu) == 0) + (((w >> 8) & 0xFFu) == 0) + (((w >> 16) & 0xFFu) == 0) + ((w >> 24) == 0);
+    } else {
+      for (uint32_t b = 0; b < 4 && r + b < n; b++) starts += rl[r + b] == 0;
+    }
+  }
+  uint32_t total;
+  (void)wave_excl_scan_u32(starts, &total);
+  if (lane == 0) {
+    gst(&S.tiles(RA_RECS, ci)[tile], (uint64_t)total);
+    if (tile == 0) gst(&S.flags[ci], (uint64_t)(rl[0] != 0));  // a column does not begin inside a record
+  }
+}
+
+// ---- k_rtake_scan ----------------------------------------------------------------------------
+// Workgroup (c, w) scans array first + w of record c over the record's own tiles. Arrays nothing was
+// counted into are left alone. Record n_cols of RA_KEEP is the caller's bitmap over n_rows.
+__global__ __launch_bounds__(256) void k_rtake_scan(uint64_t* __restrict__ scratch, uint64_t n_tiles,
+                                                    const TakeRecDev* __restrict__ recs, uint32_t n_cols, uint64_t n_rows,
+                                                    uint32_t first) {
+  const RecScratch S = rec_scratch(scratch, n_tiles, n_cols);
+  const uint32_t ci = blockIdx.x, which = first + blockIdx.y;
+  uint64_t n = n_rows;
+  if (ci < n_cols) {
+    const TakeRecDev& r = recs[ci];
+    if (r.c.kind == TAKE_MISSING) return;
+    if ((which == RA_RANK || which == RA_KEPT) && !r.c.dl) return;
+    if (which == RA_BYTES && r.c.kind != TAKE_BINARY) return;
+    if (which == RA_RECS && !r.rl) return;
+    n = r.n;
+  } else if (which != RA_KEEP) {
+    return;
+  }
+  const uint64_t total = block_excl_scan_u64<TS_PER>(S.tiles(which, ci), (n + TT_ROWS - 1) / TT_ROWS);
+  if (threadIdx.x == 0) gst(S.total(which, ci), total);
+}
+
+// ---- k_rec_expand ----------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * TT_WPB) void k_rec_expand(const uint64_t* __restrict__ bitmap, uint64_t n_rows,
+                                                            const TakeRecDev* __restrict__ recs, uint32_t n_cols,
+                                                            uint64_t n_tiles, uint64_t* __restrict__ scratch) {
+  const RecScratch S = rec_scratch(scratch, n_tiles, n_cols);
+  const uint32_t ci = blockIdx.y;
+  const uint8_t* __restrict__ rl = recs[ci].rl;
+  if (!rl) return;
+  const uint64_t n = recs[ci].n;
+  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
+  if (tile * TT_ROWS >= n) return;
+  const uint32_t lane = lane_id();
+  const uint64_t row0 = tile * TT_ROWS;
+  uint64_t run = S.tiles(RA_RECS, ci)[tile];  // record starts before the step
+  uint64_t my_word = 0;
+  constexpr uint32_t G = TG_GROUP;  // steps whose loads are issued together
+  for (uint32_t g = 0; g < TT_STEPS; g += G) {
+    const uint64_t r0 = row0 + g * 64u;
+    if (r0 >= n) break;
+    uint8_t rep[G];
+    uint64_t word[G];
+    uint32_t sh[G];
+#pragma unroll
+    for (uint32_t i = 0; i < G; i++) {
+      const uint64_t slot = r0 + i * 64u + lane;
+      rep[i] = slot < n ? rl[slot] : 1;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < G; i++) {
+      const bool in = r0 + i * 64u + lane < n;
+      const uint64_t start = __ballot(in && rep[i] == 0);
+      // starts up to and including this slot, minus 1: before the column's first start it wraps to
+      // 2^64 - 1, which no n_rows exceeds
+      const uint64_t rec = run + take_lanes_below(start) + ((start >> lane) & 1ull) - 1ull;
+      run += (uint32_t)__popcll(start);
+      const bool ok = in && rec < n_rows;
+      word[i] = ok ? bitmap[rec >> 6] : 0;
+      sh[i] = (uint32_t)(rec & 63u);
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < G; i++) {
+      const uint64_t keep = __ballot((word[i] >> sh[i]) & 1ull);
+      if (lane == g + i) my_word = keep;
+    }
+  }
+  gst(&S.slots[recs[ci].slot_off + tile * TT_STEPS + lane], my_word);
+}
+
+// ---- k_rtake_count ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * TT_WPB) void k_rtake_count(const uint64_t* __restrict__ bitmap, uint64_t n_rows,
+                                                             const TakeRecDev* __restrict__ recs, uint32_t n_cols,
+                                                             uint64_t n_tiles, uint64_t* __restrict__ scratch) {
+  const RecScratch S = rec_scratch(scratch, n_tiles, n_cols);
+  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
+  const uint32_t ci = blockIdx.y;
+  const uint64_t* bm = bitmap;
+  uint64_t n = n_rows;
+  const uint8_t* __restrict__ dl = nullptr;
+  uint32_t md = 0;
+  if (ci < n_cols) {
+    if (recs[ci].c.kind == TAKE_MISSING) return;
+    bm = rec_bitmap(recs[ci], S);
+    n = recs[ci].n;
+    dl = recs[ci].c.dl;
+    md = (uint32_t)recs[ci].c.max_def;
+  }
+  if (tile * TT_ROWS >= n) return;
+  uint32_t t_valid, t_kept, t_keep;
+  take_count_tile(bm, n, tile, dl, md, t_valid, t_kept, t_keep);
+  if (lane_id() == 0) {
+    gst(&S.tiles(RA_KEEP, ci)[tile], (uint64_t)t_keep);
+    if (dl) {
+      gst(&S.tiles(RA_RANK, ci)[tile], (uint64_t)t_valid);
+      gst(&S.tiles(RA_KEPT, ci)[tile], (uint64_t)t_kept);
+    }
+  }
+}
+
+// ---- k_rtake_bytes ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * TT_WPB) void k_rtake_bytes(const TakeRecDev* __restrict__ recs, uint32_t n_cols,
+                                                             uint64_t n_tiles, uint64_t* __restrict__ scratch) {
+  const RecScratch S = rec_scratch(scratch, n_tiles, n_cols);
+  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
+  const uint32_t ci = blockIdx.y;
+  if (recs[ci].c.kind != TAKE_BINARY) return;
+  const uint64_t n = recs[ci].n;
+  if (tile * TT_ROWS >= n) return;
+  const TakeColDev c = recs[ci].c;
+  const uint64_t sum =
+      take_bytes_tile(rec_bitmap(recs[ci], S), n, tile, c, c.dl ? S.tiles(RA_RANK, ci)[tile] : tile * TT_ROWS);
+  if (lane_id() == 63) gst(&S.tiles(RA_BYTES, ci)[tile], sum);
+}
+
+// ---- k_rtake_finish --------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_rtake_finish(const TakeRecDev* __restrict__ recs, uint32_t n_cols, uint64_t n_rows,
+                                                     uint64_t rows_capacity, uint64_t n_tiles, uint64_t* __restrict__ scratch,
+                                                     pqg_take_record_counts* __restrict__ counts,
+                                                     pqg_take_result* __restrict__ result) {
+  const RecScratch S = rec_scratch(scratch, n_tiles, n_cols);
+  const uint32_t ci = threadIdx.x;
+  const uint64_t n_keep = *S.total(RA_KEEP, n_cols);  // kept records
+  bool bad = false;
+  if (ci < n_cols) {
+    const TakeRecDev& r = recs[ci];
+    const TakeColDev& c = r.c;
+    uint64_t n_records = 0, n_slots = 0, n_out = 0, n_bytes = 0;
+    if (c.kind != TAKE_MISSING) {
+      n_slots = *S.total(RA_KEEP, ci);
+      n_out = c.dl ? *S.total(RA_KEPT, ci) : n_slots;
+      if (c.dl && *S.total(RA_RANK, ci) != c.n_values) bad = true;  // slots with a value differ from n_values
+      if (c.kind == TAKE_BINARY) n_bytes = *S.total(RA_BYTES, ci);
+      if (n_out > c.cap_values || n_bytes > c.cap_bytes) bad = true;
+      if (c.kind == TAKE_BINARY && n_out <= c.cap_values) gst((int64_t*)c.out_values + n_out, (int64_t)n_bytes);
+      if (r.rl) {
+        n_records = *S.total(RA_RECS, ci);
+        if (n_records != n_rows) bad = true;             // the column's records are not the bitmap's
+        if (r.n && S.flags[ci]) bad = true;              // slot 0 continues a record
+        if (n_slots > r.cap_levels) bad = true;          // the kept slots do not fit
+      } else {
+        n_records = n_rows;
+      }
+    }
+    if (n_keep > rows_capacity) bad = true;  // the kept records do not fit: counts against every column
+    counts[ci].n_records = n_records;
+    counts[ci].n_slots = n_slots;
+    counts[ci].n_values = n_out;
+    counts[ci].n_bytes = n_bytes;
+  }
+  const uint64_t bad_cols = __ballot(bad);
+  if (threadIdx.x == 0) {
+    result->n_rows = n_keep;
+    const bool err = bad_cols != 0 || n_keep > rows_capacity;
+    result->error = err ? PQG_ERR_INVALID_ARG : PQG_OK;
+    result->error_column = bad_cols ? (int32_t)__builtin_ctzll(bad_cols) : -1;
+  }
+}
+
+// ---- k_rtake_gather --------------------------------------------------------------------------
+template <bool STAGED>
+__global__ __launch_bounds__(64 * TT_WPB) void k_rtake_gather(const TakeRecDev* __restrict__ recs, uint32_t n_cols,
+                                                              uint64_t n_tiles, const uint64_t* __restrict__ scratch) {
+  __shared__ __align__(16) uint8_t lds_all[TT_WPB * TG_LDS_WAVE];
+  const RecScratch S = rec_scratch(const_cast<uint64_t*>(scratch), n_tiles, n_cols);
+  const uint64_t tile = (uint64_t)blockIdx.x * TT_WPB + wave_id();
+  const uint32_t ri = blockIdx.y;  // n_cols columns, then the repetition bytes of the repeated ones
+  if (recs[ri].c.kind == TAKE_MISSING) return;
+  const uint64_t n = recs[ri].n;
+  if (tile * TT_ROWS >= n) return;
+  const TakeColDev c = recs[ri].c;
+  const uint32_t kc = recs[ri].keep_col;
+  uint8_t* lds = lds_all + wave_id() * TG_LDS_WAVE;
+  TakeTile t;
+  t.row0 = tile * TT_ROWS;
+  t.n_rows = n;
+  t.my_word = tile_word(rec_bitmap(recs[ri], S), n, tile);
+  if (__ballot(t.my_word != 0) == 0) return;  // the tile keeps nothing
+  t.rows_capacity = recs[ri].cap_levels;
+  t.row_out0 = S.tiles(RA_KEEP, kc)[tile];
+  t.rank0 = c.dl ? S.tiles(RA_RANK, ri)[tile] : t.row0;
+  t.val0 = c.dl ? S.tiles(RA_KEPT, ri)[tile] : t.row_out0;
+  t.byte0 = c.kind == TAKE_BINARY ? S.tiles(RA_BYTES, ri)[tile] : 0;
+  switch (c.kind) {
+    case TAKE_W1: gather_fixed<uint8_t, STAGED>(c, t, lds); break;
+    case TAKE_W4: gather_fixed<uint32_t, STAGED>(c, t, lds); break;
+    case TAKE_W8: gather_fixed<uint64_t, STAGED>(c, t, lds); break;
+    case TAKE_GENERIC: gather_generic<STAGED>(c, t, lds); break;
+    default: gather_binary<STAGED>(c, t, lds); break;
+  }
+}
+
+// ---- launch ----------------------------------------------------------------------------------
+hipError_t launch_take_records(hipStream_t st, const uint64_t* bitmap, uint64_t n_rows, const TakeRecDev* d_recs,
+                               uint32_t n_cols, const TakeRecPlan& plan, uint64_t rows_capacity, uint64_t* scratch,
+                               pqg_take_record_counts* counts, pqg_take_result* result, bool staged) {
+  const uint64_t n_tiles = filter_tiles(plan.max_rows);
+  const uint32_t wgs = (uint32_t)((n_tiles + TT_WPB - 1) / TT_WPB);
+  const dim3 wg(64 * TT_WPB);
+  if (plan.any_repeated) {
+    if (n_tiles) hipLaunchKernelGGL(k_rec_count, dim3(wgs, n_cols), wg, 0, st, d_recs, n_cols, n_tiles, scratch);
+    hipLaunchKernelGGL(k_rtake_scan, dim3(n_cols, 1), dim3(256), 0, st, scratch, n_tiles, d_recs, n_cols, n_rows,
+                       (uint32_t)RA_RECS);
+    if (n_tiles)
+      hipLaunchKernelGGL(k_rec_expand, dim3(wgs, n_cols), wg, 0, st, bitmap, n_rows, d_recs, n_cols, n_tiles, scratch);
+  }
+  if (n_tiles)
+    hipLaunchKernelGGL(k_rtake_count, dim3(wgs, n_cols + 1), wg, 0, st, bitmap, n_rows, d_recs, n_cols, n_tiles, scratch);
+  hipLaunchKernelGGL(k_rtake_scan, dim3(n_cols + 1, plan.any_nullable ? 3 : 1), dim3(256), 0, st, scratch, n_tiles, d_recs,
+                     n_cols, n_rows, (uint32_t)RA_KEEP);
+  if (plan.any_binary) {
+    if (n_tiles) hipLaunchKernelGGL(k_rtake_bytes, dim3(wgs, n_cols), wg, 0, st, d_recs, n_cols, n_tiles, scratch);
+    hipLaunchKernelGGL(k_rtake_scan, dim3(n_cols, 1), dim3(256), 0, st, scratch, n_tiles, d_recs, n_cols, n_rows,
+                       (uint32_t)RA_BYTES);
+  }
+  hipLaunchKernelGGL(k_rtake_finish, dim3(1), dim3(64), 0, st, d_recs, n_cols, n_rows, rows_capacity, n_tiles, scratch, counts,
+                     result);
+  if (n_tiles && plan.n_records) {
+    if (staged)
+      hipLaunchKernelGGL(k_rtake_gather<true>, dim3(wgs, plan.n_records), wg, 0, st, d_recs, n_cols, n_tiles, scratch);
+    else
+      hipLaunchKernelGGL(k_rtake_gather<false>, dim3(wgs, plan.n_records), wg, 0, st, d_recs, n_cols, n_tiles, scratch);
   }
   return hipGetLastError();
 }

@@ -1,7 +1,8 @@
-// pqgpu_take_host.cpp — host half of pqg_take (include/pqgpu.h, "row selection"): the refusals made
-// before any launch and the per-column table for the kernels. Plain C++ with no HIP in it, so that it
-// also builds alone under the sanitizers (tests/c/take_sanitize.cpp). No pointer is dereferenced
-// except `cols`.
+// pqgpu_take_host.cpp — host half of pqg_take and pqg_take_records (include/pqgpu.h, "row selection",
+// "record selection on repeated columns"): the refusals made before any launch and the per-column table
+// for the kernels. Plain C++ with no HIP in it, so that it also builds alone under the sanitizers
+// (tests/c/take_sanitize.cpp, tests/c/take_records_sanitize.cpp). No pointer is dereferenced except
+// `cols`.
 #include "pqgpu_take.h"
 
 namespace pqg {
@@ -61,6 +62,76 @@ int take_validate(bool have_ctx, const uint64_t* d_bitmap, uint64_t n_rows, cons
     d.cap_bytes = binary ? c.out_binary_capacity : 0;
     tab[i] = d;
   }
+  return PQG_OK;
+}
+
+int take_records_validate(bool have_ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_record_column* cols,
+                          int n_cols, uint64_t out_rows_capacity, const pqg_take_record_counts* d_counts,
+                          const pqg_take_result* d_result, TakeRecDev* tab, TakeRecPlan* plan) {
+  if (!have_ctx || !d_result || !d_counts || !plan || n_cols < 0 || (n_cols > 0 && !cols)) return PQG_ERR_INVALID_ARG;
+  if (n_rows && !d_bitmap) return PQG_ERR_INVALID_ARG;
+  if (!aligned(d_bitmap, 8) || !aligned(d_counts, 8) || !aligned(d_result, 8)) return PQG_ERR_INVALID_ARG;
+  if (n_cols > PQG_TAKE_MAX_COLUMNS) return PQG_ERR_UNSUPPORTED;
+  TakeRecPlan p{};
+  p.n_records = (uint32_t)n_cols;
+  p.max_rows = n_rows;
+  constexpr uint64_t tile = PQG_FILTER_TILE_ROWS;
+  for (int i = 0; i < n_cols; i++) {
+    const pqg_take_record_column& rc = cols[i];
+    const bool missing = rc.col.max_def > 0 && !rc.col.def_levels;
+    if (rc.max_rep < 0 || rc.max_rep > 254 || rc.reserved != 0) return PQG_ERR_INVALID_ARG;
+    // take_validate on `col`; the level bytes of a repeated column are bounded by its own capacity
+    const uint64_t n = rc.max_rep > 0 ? rc.n_slots : n_rows;
+    const uint64_t level_cap = rc.max_rep > 0 ? rc.out_slots_capacity : out_rows_capacity;
+    TakeRecDev d{};
+    const int e = take_validate(true, d_bitmap, n_rows, &rc.col, 1, level_cap, (const pqg_take_counts*)d_counts, d_result,
+                                &d.c);
+    if (e != PQG_OK) return e;
+    if (rc.max_rep > 0) {
+      if (rc.col.max_def == 0) return PQG_ERR_INVALID_ARG;  // a repeated node always adds a definition level
+      if (!missing) {
+        if (!rc.rep_levels) return PQG_ERR_INVALID_ARG;
+        if (rc.out_slots_capacity && (!rc.out_rep_levels || !rc.col.out_def_levels)) return PQG_ERR_INVALID_ARG;
+        if (rc.n_slots > UINT64_MAX - tile) return PQG_ERR_INVALID_ARG;  // its tiles cannot be counted
+      }
+    } else {
+      if (rc.rep_levels || rc.n_slots != n_rows) return PQG_ERR_INVALID_ARG;
+    }
+    if (!missing && rc.n_slots < n_rows) return PQG_ERR_INVALID_ARG;  // a record has at least one slot
+    d.keep_col = (uint32_t)i;
+    d.cap_levels = level_cap;
+    d.n = missing ? 0 : n;
+    d.bitmap = d_bitmap;
+    if (!missing) {
+      p.any_nullable |= d.c.dl != nullptr;
+      p.any_binary |= d.c.kind == TAKE_BINARY;
+      if (d.n > p.max_rows) p.max_rows = d.n;
+    }
+    if (rc.max_rep > 0 && !missing) {
+      d.rl = rc.rep_levels;
+      d.bitmap = nullptr;
+      d.own_bitmap = 1;
+      d.slot_off = p.slot_words;
+      p.slot_words += (rc.n_slots + tile - 1) / tile * (tile / 64);
+      p.any_repeated = true;
+      // the repetition bytes: a required 1-byte column over the same slots
+      TakeRecDev r{};
+      r.c.kind = TAKE_W1;
+      r.c.width = 1;
+      r.c.values = rc.rep_levels;
+      r.c.n_values = rc.n_slots;
+      r.c.out_values = rc.out_rep_levels;
+      r.c.cap_values = rc.out_rep_levels ? rc.out_slots_capacity : 0;
+      r.n = rc.n_slots;
+      r.cap_levels = 0;
+      r.own_bitmap = 1;
+      r.slot_off = d.slot_off;
+      r.keep_col = (uint32_t)i;
+      tab[p.n_records++] = r;
+    }
+    tab[i] = d;
+  }
+  *plan = p;
   return PQG_OK;
 }
 

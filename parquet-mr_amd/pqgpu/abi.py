@@ -293,3 +293,17 @@ class TakeResult(C.Structure):
 
 
 assert C.sizeof(TakeColumn) == 88 and C.sizeof(TakeCounts) == 16 and C.sizeof(TakeResult) == 16
+
+
+class TakeRecordColumn(C.Structure):
+    """pqg_take_record_column (128 bytes): a pqg_take_column plus the column's repetition levels."""
+    _fields_ = [("col", TakeColumn), ("max_rep", C.c_int32), ("reserved", C.c_int32), ("rep_levels", C.c_void_p),
+                ("n_slots", C.c_uint64), ("out_rep_levels", C.c_void_p), ("out_slots_capacity", C.c_uint64)]
+
+
+class TakeRecordCounts(C.Structure):
+    """pqg_take_record_counts (32 bytes, device-resident, one per column)."""
+    _fields_ = [("n_records", C.c_uint64), ("n_slots", C.c_uint64), ("n_values", C.c_uint64), ("n_bytes", C.c_uint64)]
+
+
+assert C.sizeof(TakeRecordColumn) == 128 and C.sizeof(TakeRecordCounts) == 32

@@ -44,6 +44,8 @@ class DeviceColumn:
         self.n_values = 0
         self.max_def = 0 if def_levels is None else 1  # alloc_columns sets the column's own
         self.flags = 0                                 # pqg_column_desc.flags (COLUMN_DICTIONARY_IDS)
+        self.max_rep = 0     # a repeated leaf: decode() sets the column's own
+        self.n_slots = None  # level bytes behind def_levels / rep_levels (decode(); a flat column: its rows)
         self.dictionary = None  # an id column's decoded dictionary (Decoder.decode_dictionary), set by the caller
 
     def offsets(self):
@@ -349,6 +351,8 @@ class Decoder:
             cols.append(DeviceColumn(cd["physical_type"], vals, dl, rl, cd["type_length"], binary))
             cols[-1].max_def = int(cd["max_def"])
             cols[-1].flags = int(cd.get("flags", 0))
+            cols[-1].max_rep = int(cd["max_rep"])
+            cols[-1].n_slots = int(n)
         return cols
 
     def _descs(self, batch, cols):
@@ -385,6 +389,8 @@ class Decoder:
             cols[i].binary_data = torch.empty(int(st.value_index) + 64, dtype=torch.uint8, device=self.device)
         for i, col in enumerate(cols):
             col.n_values = int(descs[i].values_written)
+            col.max_rep = int(batch.columns[i]["max_rep"])
+            col.n_slots = int(batch.column_slots[i])
         if check:
             native.check(rc, st, "pqg_decode")
         return cols, st
@@ -646,6 +652,18 @@ class Decoder:
         abi.TAKE_MAX_COLUMNS columns are split over several calls."""
         from . import take as T
         return T.take(self, selection, cols, n_rows, rows_capacity, out)
+
+    def take_records(self, selection, cols, n_rows=None, rows_capacity=None, out=None):
+        """Keep whole records (pqg_take_records): the bitmap names records, and every column loses the
+        same ones, repeated leaves included, as RecordReaderImplementation.read drops the records a
+        filter or the RowRanges skip. selection / n_rows / rows_capacity as for take(). cols: the
+        DeviceColumns decode() returned, flat or repeated (rep_levels, def_levels, n_slots, n_values),
+        or filter.MissingColumns. out: one take.RecordOutput per column. Asynchronous on the decoder's
+        stream; returns a take.TakenRecords whose `n_rows` / `columns` wait for it; the columns are valid
+        inputs to take_records again and their levels to assemble(). More than abi.TAKE_MAX_COLUMNS
+        columns are split over several calls."""
+        from . import take as T
+        return T.take_records(self, selection, cols, n_rows, rows_capacity, out)
 
     # -- record assembly -------------------------------------------------------------
     def assemble(self, path, n_slots, def_levels=None, rep_levels=None):

@@ -36,6 +36,8 @@ EXPORTS = [
     "pqg_filter_run_dict", "pqg_decode_dictionary",
     # row selection (the rows a bitmap keeps, as compact columns)
     "pqg_take",
+    # ... with repeated columns: whole records
+    "pqg_take_records",
 ]
 
 
@@ -111,6 +113,7 @@ def lib():
         L.pqg_filter_run_dict.argtypes = [vp, vp, vp, vp, i32, u64, vp, vp, u64, vp]
         L.pqg_decode_dictionary.argtypes = [vp, vp, u64, vp, C.POINTER(abi.Status)]
         L.pqg_take.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
+        L.pqg_take_records.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
         L.pqg_error_name.argtypes = [i32]
         L.pqg_error_name.restype = C.c_char_p
         if L.pqg_abi_version() != abi.ABI_VERSION:
