@@ -36,7 +36,8 @@
  *
  * ABI 6 (this version): the rows a selection bitmap keeps, gathered into compact columns on the
  * device (pqg_take; PQG_DISPATCH_TAKE_STAGED). Added to ABI 6 without a change to what it had:
- * record filters on dictionary-id columns (pqg_filter_dictionary, pqg_filter_run_dict,
+ * record filters on list columns (PQG_FILTER_CONTAINS, pqg_filter_record_column,
+ * pqg_filter_run_records); record filters on dictionary-id columns (pqg_filter_dictionary, pqg_filter_run_dict,
  * PQG_FILTER_DICT_LDS_BYTES) and pqg_decode_dictionary; record selection on repeated columns
  * (pqg_take_record_column, pqg_take_record_counts, pqg_take_records).
  * ABI 5: record-level filter2 predicates over decoded columns (pqg_filter_create /
@@ -661,8 +662,9 @@ int pqg_pages_from_headers(const pqg_page_header* headers, int n_headers, int co
  * FilteringRecordMaterializer do value by value through IncrementallyUpdatedFilterPredicate
  * (filter2/recordlevel/IncrementallyUpdatedFilterPredicateEvaluator.java:45-61 and the generated
  * ValueInspectors, parquet-generator/.../IncrementallyUpdatedFilterPredicateGenerator.java:198-327).
- * Flat columns only (max_rep == 0); a row is null when its definition level is below max_def, and a
- * column no value reached (missing from the file) is null in every row.
+ * pqg_filter_run and pqg_filter_run_dict take flat columns only (max_rep == 0); a row is null when its
+ * definition level is below max_def, and a column no value reached (missing from the file) is null in
+ * every row. A repeated column is reached through contains() and pqg_filter_run_records (below).
  *
  * The predicate is an array of nodes in post-order (children before parents, one root: the last
  * node; every other node is the child of exactly one node). pqg_filter_create validates it and
@@ -696,7 +698,8 @@ enum pqg_filter_op {
   PQG_FILTER_NOTIN = 7,
   PQG_FILTER_AND = 8,
   PQG_FILTER_OR = 9,
-  PQG_FILTER_NOT = 10
+  PQG_FILTER_NOT = 10,
+  PQG_FILTER_CONTAINS = 11 /* unary, on a repeated column: see "record filter on list columns" below */
 };
 
 #define PQG_FILTER_NULL_LITERAL 1 /* eq / notEq: the literal is null; in / notIn: the set contains null */
@@ -803,6 +806,68 @@ int pqg_filter_run_dict(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter
                         const pqg_filter_dictionary* dicts, int n_cols, uint64_t n_rows, uint64_t* d_bitmap,
                         int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result);
 
+/* ---- record filter on list columns: contains() (an addition to ABI 6) ------------------------------
+ * FilterApi.contains(pred) (filter2/predicate/FilterApi.java:262, Operators.Contains,
+ * Operators.java:326-462) is the one filter2 predicate that names a repeated column
+ * (SchemaCompatibilityValidator.java:177-214 requires maxRepetitionLevel > 0 for it and refuses every
+ * other predicate there). It is evaluated record by record (ContainsPredicate and the
+ * expectMultipleResults inspectors, IncrementallyUpdatedFilterPredicateGenerator.java:198-327, 339-537).
+ *
+ * The node: op PQG_FILTER_CONTAINS, `left` = a leaf node (eq .. notIn) on the repeated column, right = -1,
+ * column = -1, no flags, no literals. contains(L) holds on a record iff some slot of the record has
+ * def == max_def and L's comparison holds on that slot's value (the comparison a flat leaf makes on a row
+ * that has a value). A slot without a value never counts (a null element, an empty list, a null list),
+ * so a record with no matching value is false for every op, notEq and notIn included
+ * (ContainsPredicate.updateNull), unlike flat notEq. notIn means "some value is not a member of the set",
+ * the flat filter's reading of notIn applied per value. A column missing from the file is false in every
+ * record. and / or above contains nodes stay plain and / or (ContainsAndPredicate is true iff both inner
+ * inspectors became true, each over every value of the record: and(contains(l), contains(r))).
+ *
+ * pqg_filter_create refuses, in the reference's order (LogicalInverseRewriter, then ContainsRewriter,
+ * FilterCompat.java:80-91); pqg_status.value_index names the node:
+ *   PQG_ERR_INVALID_ARG  a contains node whose child is not a leaf, or with right != -1, flags or literals
+ *                        of its own; a child with PQG_FILTER_NULL_LITERAL (Operators.java:429-435)
+ *   PQG_ERR_UNSUPPORTED  a NOT anywhere above a contains (LogicalInverter.java:97-99)
+ *   ContainsRewriter.visit(And / Or) on the NOT-free tree from the root (ContainsRewriter.java:100-168):
+ *   a side that is a plain leaf returns at once (the other side is not examined); a left side that
+ *   rewrites to a Contains with a right side that does not is PQG_ERR_UNSUPPORTED ("cannot be composed
+ *   with non-Contains predicates"; the mirror case is accepted); two Contains sides on different columns
+ *   are PQG_ERR_INVALID_ARG (Operators.java:377-385).
+ * pqg_filter_program reports contains nodes as they are; they count against PQG_FILTER_MAX_NODES. A
+ * filter with a contains node is PQG_ERR_INVALID_ARG for pqg_filter_run and pqg_filter_run_dict. */
+typedef struct pqg_filter_record_column { /* sizeof == 64 */
+  pqg_filter_column col;     /* def_levels: one byte per SLOT for a repeated column */
+  int32_t max_rep;           /* 0: flat (rep_levels NULL, n_slots == n_rows) */
+  int32_t reserved;          /* 0 */
+  const uint8_t* rep_levels; /* device, one byte per slot */
+  uint64_t n_slots;
+} pqg_filter_record_column;
+
+/* pqg_filter_run_dict over records: n_rows counts RECORDS, a repeated column is a stripe of slots as
+ * for pqg_take_records, and the outputs are exactly those of pqg_filter_run indexed by record, so
+ * d_bitmap goes straight into pqg_take_records on the same ctx. Only the columns the predicate names are
+ * read. Without a contains node and with flat columns only the outputs are byte-identical to
+ * pqg_filter_run_dict. `dicts` as there (may be NULL); a repeated column may hold dictionary ids.
+ * Refused before any launch, PQG_ERR_INVALID_ARG: everything pqg_filter_run_dict refuses; a contains leaf
+ * on a present column with max_rep == 0; any other leaf on a column with max_rep > 0; max_rep outside
+ * 0..254, non-zero `reserved`, max_rep > 0 with max_def == 0 or without rep_levels, n_slots < n_rows,
+ * max_rep == 0 with rep_levels or with n_slots != n_rows. A missing column (max_def > 0, def_levels NULL)
+ * is exempt from these. d_result->error = PQG_ERR_INVALID_ARG with error_column the lowest bad column the
+ * predicate names when slot 0 of a repeated column has rep != 0, its record starts differ in number from
+ * n_rows, or its slots with def == max_def differ in number from n_values (and as for pqg_filter_run on
+ * flat columns); PQG_ERR_DICT_ID as for pqg_filter_run_dict, with lower precedence. In every case no load
+ * leaves [0, n_slots), [0, n_values), the dictionary or the bitmap's ceil(n_rows / 64) words; a slot
+ * whose record index is -1 or >= n_rows contributes nothing.
+ * Launches, none of which waits on another workgroup and whose number does not depend on n_cols: with
+ * contains leaves, the record starts and values per (repeated column, tile of PQG_FILTER_TILE_ROWS
+ * slots), their scans, and one record bitmap per contains leaf (a wave per tile and group of up to four
+ * contains leaves of one column, which share one load of the value; at most two 64-bit atomic ORs per
+ * leaf and wave, for the words a record spanning tiles shares); then the launches of
+ * pqg_filter_run_dict, whose evaluation reads a contains node's 64 records as one word of that bitmap. */
+int pqg_filter_run_records(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_record_column* cols,
+                           const pqg_filter_dictionary* dicts, int n_cols, uint64_t n_rows, uint64_t* d_bitmap,
+                           int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result);
+
 /* Decode the dictionary page `col` names (dict_offset, dict_size, dict_num_values, dict_encoding,
  * physical_type, type_length; d_bytes / n_bytes as for pqg_decode) into col->values / col->binary_data
  * within values_capacity / binary_capacity, any physical type: the PLAIN values of a required column
@@ -890,9 +955,10 @@ int pqg_take(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_
  * nested leaves included. That is what the reference does: RecordReaderImplementation.read drops a
  * whole record when shouldSkipCurrentRecord says so (RecordReaderImplementation.java:440-449,
  * FilteringRecordMaterializer), and SynchronizingColumnReader skips the rows outside the RowRanges;
- * both act on records. Its record filter cannot name a repeated column (SchemaCompatibilityValidator:
- * "FilterPredicates do not currently support repeated columns"), but the filter's result applies to all
- * columns of the record: the normal case is a filter on flat columns and a take on every column.
+ * both act on records. Of its record filters only contains() can name a repeated column
+ * (SchemaCompatibilityValidator: "FilterPredicates do not currently support repeated columns" for every
+ * other predicate), but the filter's result applies to all columns of the record: the normal case is a
+ * filter on flat columns, or a contains() on a list, and a take on every column.
  *
  * A repeated leaf is a stripe of SLOTS (one repetition byte and one definition byte per slot, dense
  * values for the slots with def == max_def), as pqg_decode writes it. Record i of a column is the run of
@@ -943,7 +1009,8 @@ typedef struct pqg_take_record_counts {
  * the record bitmap into one slot bitmap per repeated column; then the launches of pqg_take with every
  * column on its own bitmap (a flat column on d_bitmap, a repeated one on its slot bitmap, its repetition
  * bytes gathered as a required 1-byte column on the same bitmap). PQG_DISPATCH_TAKE_STAGED applies.
- * Not covered: a record filter on a repeated column (the reference refuses it) and contains(). */
+ * The record filter that looks inside a list is contains() (pqg_filter_run_records, above); its bitmap
+ * is a valid d_bitmap here on the same ctx without synchronisation. */
 int pqg_take_records(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_record_column* cols,
                      int n_cols, uint64_t out_rows_capacity, pqg_take_record_counts* d_counts,
                      pqg_take_result* d_result);

@@ -1544,15 +1544,21 @@ static_assert(sizeof(pqg_filter_node) == 32 && sizeof(pqg_filter_column) == 40 &
               "filter ABI layout");
 
 static_assert(sizeof(pqg_filter_dictionary) == 24, "filter dictionary ABI layout");
+static_assert(sizeof(pqg_filter_record_column) == 64, "filter record column ABI layout");
 
-// The launches of pqg_filter_run / pqg_filter_run_dict once pqg::filter_bind has accepted the columns.
+// The launches of pqg_filter_run / pqg_filter_run_dict once pqg::filter_bind has accepted the columns, and
+// with `rec` (whose dt is `dt`) those of pqg_filter_run_records with contains leaves.
 static int filter_launch(pqg_ctx* ctx, const pqg_filter* filter, const pqg::FilterCols& fc, const pqg::FilterDictTab* dt,
                          uint64_t n_rows, uint64_t* d_bitmap, int64_t* d_row_ids, uint64_t row_ids_capacity,
-                         pqg_filter_result* d_result) {
+                         pqg_filter_result* d_result, pqg::FilterRecDev* rec = nullptr) {
   if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
   const uint64_t dict_words = dt ? PQG_FILTER_MAX_NODES + dt->table_words : 0;
-  if (ctx->filter_scratch.ensure(8 * (size_t)pqg::filter_scratch_words(n_rows, fc.n_nullable, dict_words)) != hipSuccess)
-    return PQG_ERR_HIP;
+  const uint64_t scratch_words =
+      rec ? pqg::filter_records_scratch_words(n_rows, fc.n_nullable, dict_words, rec->rt.n_leaves, rec->rt.n_rep,
+                                              rec->rt.max_slots)
+          : pqg::filter_scratch_words(n_rows, fc.n_nullable, dict_words);
+  if (ctx->filter_scratch.ensure(8 * (size_t)scratch_words) != hipSuccess) return PQG_ERR_HIP;
+  if (rec) rec->rt.bitmaps = pqg::filter_records_bitmaps((uint64_t*)ctx->filter_scratch.p, n_rows, fc.n_nullable, dict_words);
   if (ctx->filter_serial != filter->serial) {
     if (ctx->filter_image.ensure(filter->image.size()) != hipSuccess) return PQG_ERR_HIP;
     ctx->filter_serial = 0;
@@ -1564,7 +1570,8 @@ static int filter_launch(pqg_ctx* ctx, const pqg_filter* filter, const pqg::Filt
   if (dt) {
     // the dictionary table goes up like pqg_take's column table: through a pinned slot that is reused
     // once the copy out of it has run
-    constexpr size_t slot_bytes = sizeof(pqg::FilterDictTab);
+    constexpr size_t slot_bytes = sizeof(pqg::FilterRecDev);  // a FilterDictTab, or the FilterRecDev it begins
+    const size_t tab_bytes = rec ? sizeof(pqg::FilterRecDev) : sizeof(pqg::FilterDictTab);
     if (ctx->filter_dict.ensure(slot_bytes) != hipSuccess || ctx->filter_dict_pin.ensure(slot_bytes * pqg_ctx::TAKE_SLOTS) != hipSuccess)
       return PQG_ERR_HIP;
     const uint32_t slot = ctx->filter_dict_seq++ % pqg_ctx::TAKE_SLOTS;
@@ -1575,10 +1582,17 @@ static int filter_launch(pqg_ctx* ctx, const pqg_filter* filter, const pqg::Filt
       return PQG_ERR_HIP;
     }
     void* pin = (uint8_t*)ctx->filter_dict_pin.p + slot * slot_bytes;
-    std::memcpy(pin, dt, slot_bytes);
-    if (hipMemcpyAsync(ctx->filter_dict.p, pin, slot_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+    std::memcpy(pin, rec ? (const void*)rec : (const void*)dt, tab_bytes);
+    if (hipMemcpyAsync(ctx->filter_dict.p, pin, tab_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipEventRecord(ev, ctx->stream) != hipSuccess)
       return PQG_ERR_HIP;
+  }
+  if (rec) {
+    const hipError_t e = pqg::launch_filter_records(
+        ctx->stream, (const uint8_t*)ctx->filter_image.p, (uint32_t)filter->image.size(), fc, n_rows,
+        (uint64_t*)ctx->filter_scratch.p, d_bitmap, d_row_ids, row_ids_capacity, d_result,
+        (const pqg::FilterRecDev*)ctx->filter_dict.p, rec);
+    return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
   }
   const hipError_t e =
       pqg::launch_filter(ctx->stream, (const uint8_t*)ctx->filter_image.p, (uint32_t)filter->image.size(), fc, n_rows,
@@ -1608,6 +1622,23 @@ int pqg_filter_run_dict(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter
   const int rc = pqg::filter_bind(filter, cols, dicts, n_cols, n_rows, &fc, &dt, &any_dict);
   if (rc != PQG_OK) return rc;
   return filter_launch(ctx, filter, fc, any_dict ? &dt : nullptr, n_rows, d_bitmap, d_row_ids, row_ids_capacity, d_result);
+}
+
+int pqg_filter_run_records(pqg_ctx* ctx, const pqg_filter* filter, const pqg_filter_record_column* cols,
+                           const pqg_filter_dictionary* dicts, int n_cols, uint64_t n_rows, uint64_t* d_bitmap,
+                           int64_t* d_row_ids, uint64_t row_ids_capacity, pqg_filter_result* d_result) {
+  if (!ctx || !filter || !d_result) return PQG_ERR_INVALID_ARG;
+  if (n_rows && !d_bitmap) return PQG_ERR_INVALID_ARG;
+  pqg::FilterCols fc;
+  pqg::FilterRecDev rec;
+  bool any_dict = false;
+  const int rc = pqg::filter_bind_records(filter, cols, dicts, n_cols, n_rows, &fc, &rec.dt, &any_dict, &rec.rt);
+  if (rc != PQG_OK) return rc;
+  // without a contains leaf every named column is flat: the launches of pqg_filter_run_dict as they are
+  if (!rec.rt.n_leaves)
+    return filter_launch(ctx, filter, fc, any_dict ? &rec.dt : nullptr, n_rows, d_bitmap, d_row_ids, row_ids_capacity,
+                         d_result);
+  return filter_launch(ctx, filter, fc, &rec.dt, n_rows, d_bitmap, d_row_ids, row_ids_capacity, d_result, &rec);
 }
 
 int pqg_decode_dictionary(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_column_desc* col, pqg_status* st) {

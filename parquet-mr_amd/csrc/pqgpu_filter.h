@@ -1,6 +1,6 @@
 // pqgpu_filter.h — the compiled form of a filter2 predicate, shared by its host half
 // (pqgpu_filter_host.cpp: validation, LogicalInverseRewriter, comparator keys; plain C++) and its
-// device half (pqgpu_filter.hip: the five launches of pqg_filter_run).
+// device half (pqgpu_filter.hip: the five launches of pqg_filter_run, and those of contains()).
 #pragma once
 #include <stdint.h>
 
@@ -74,11 +74,55 @@ static_assert(sizeof(FilterDevHeader) + PQG_FILTER_MAX_NODES * (sizeof(FilterDev
                       PQG_FILTER_MAX_LITERAL_BYTES + 16 + PQG_FILTER_DICT_LDS_BYTES <= 65536,
               "filter image + dictionary tables exceed a workgroup's LDS");
 
+// ---- pqg_filter_run_records -----------------------------------------------------------------------
+// Device-node flag (never in pqg_filter_node.flags): the leaf is the child of a CONTAINS node. The
+// evaluation kernel skips it; k_filter_contains evaluates it per slot.
+constexpr uint8_t FILTER_DEV_CONTAINED = 0x80;
+// FilterColDev::null_idx of a repeated slot (its levels are per slot, not per row: never ranked over rows)
+constexpr int32_t FILTER_NULL_IDX_REPEATED = -2;
+constexpr uint8_t FILTER_NO_LEAF = 0xFF;
+constexpr uint32_t FILTER_CONTAINS_GROUP = 4;  // contains leaves of one column a wave evaluates on one load of the value
+
+// The record facts of a run, read by the kernels from a small device table beside FilterDictTab.
+// Repeated columns the predicate names are numbered 0 .. n_rep - 1 (rep_slot), contains leaves
+// 0 .. n_leaves - 1 in program order (leaf_node: the CONTAINS node's child). A missing column has no
+// entry in rep_slot: the record bitmaps of its contains leaves stay zero. The contains leaves of a repeated
+// column are dealt to groups of up to FILTER_CONTAINS_GROUP (k_filter_contains: one wave per group and tile).
+struct FilterRecTab {
+  uint32_t n_rep;         // repeated, present slots with a contains leaf
+  uint32_t n_leaves;      // contains leaves (record bitmaps)
+  uint32_t n_groups;      // groups of contains leaves (k_filter_contains' grid.y)
+  uint32_t pad;
+  uint64_t bitmap_words;  // u64 words of one record bitmap: filter_tiles(n_rows) * 64
+  uint64_t max_slots;     // the largest n_slots of rep_slot's columns
+  uint8_t rep_slot[PQG_FILTER_MAX_NODES];     // repeated column -> program slot
+  uint8_t leaf_node[PQG_FILTER_MAX_NODES];    // contains leaf -> its leaf node
+  uint8_t leaf_rep[PQG_FILTER_MAX_NODES];     // contains leaf -> repeated column, FILTER_NO_LEAF: missing column
+  uint8_t node_leaf[PQG_FILTER_MAX_NODES];    // CONTAINS node -> contains leaf, FILTER_NO_LEAF otherwise
+  uint8_t group_rep[PQG_FILTER_MAX_NODES];    // group -> repeated column
+  uint8_t group_n[PQG_FILTER_MAX_NODES];      // group -> its leaves, 1 .. FILTER_CONTAINS_GROUP
+  uint8_t group_leaf[PQG_FILTER_MAX_NODES][FILTER_CONTAINS_GROUP];  // group -> contains leaves (unused: 0)
+  const uint8_t* rl[PQG_FILTER_MAX_NODES];    // per repeated column: repetition bytes
+  uint64_t n_slots[PQG_FILTER_MAX_NODES];     // per repeated column
+  uint64_t* bitmaps;      // device: the record bitmaps, bitmap_words each (set at launch, inside the scratch)
+};
+// What goes to the device for a run with contains leaves (k_filter_contains, k_filter_eval_records).
+struct FilterRecDev {
+  FilterDictTab dt;
+  FilterRecTab rt;
+};
+
 // Binds the caller's columns (and dictionaries, or null) to the program's slots: every refusal
 // pqg_filter_run / pqg_filter_run_dict make before a launch, the FilterCols the kernels take and, with
 // dictionaries, the FilterDictTab (`dt` may be null without them). No device calls.
 int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const pqg_filter_dictionary* dicts, int n_cols,
                 uint64_t n_rows, FilterCols* fc, FilterDictTab* dt, bool* any_dict);
+
+// The same for pqg_filter_run_records: every refusal it makes before a launch, the FilterCols (a repeated
+// slot has null_idx == FILTER_NULL_IDX_REPEATED and is not in null_slot), the FilterDictTab (`dt` is
+// required: it is filled whether or not a dictionary is given) and the FilterRecTab. No device calls.
+int filter_bind_records(const pqg_filter* filter, const pqg_filter_record_column* cols, const pqg_filter_dictionary* dicts,
+                        int n_cols, uint64_t n_rows, FilterCols* fc, FilterDictTab* dt, bool* any_dict, FilterRecTab* rt);
 
 }  // namespace pqg
 
@@ -90,6 +134,7 @@ struct pqg_filter {
   std::vector<uint8_t> bytes;           // BYTE_ARRAY literal bytes
   std::vector<int32_t> slot_column;     // slot -> column index
   std::vector<uint8_t> image;           // device image (FilterDevHeader ...)
+  bool has_contains = false;            // a CONTAINS node: pqg_filter_run_records only
 };
 
 namespace pqg {

@@ -1,8 +1,9 @@
 // pqgpu_filter_host.cpp — host half of the record filter (include/pqgpu.h, "record filter"):
-// validation of a predicate table, LogicalInverseRewriter, literal keys and the device image, and the
-// binding of a run's columns and dictionaries to the program's slots (pqg::filter_bind).
+// validation of a predicate table, LogicalInverseRewriter and ContainsRewriter's refusals, literal keys
+// and the device image, and the binding of a run's columns and dictionaries to the program's slots
+// (pqg::filter_bind, pqg::filter_bind_records).
 // Plain C++ with no HIP in it, so that it also builds alone under the sanitizers
-// (tests/c/filter_sanitize.cpp, tests/c/filter_dict_sanitize.cpp).
+// (tests/c/filter_sanitize.cpp, tests/c/filter_dict_sanitize.cpp, tests/c/filter_records_sanitize.cpp).
 #include <stdio.h>
 #include <string.h>
 
@@ -54,6 +55,60 @@ int compare_bytes(const uint8_t* a, uint32_t na, const uint8_t* b, uint32_t nb) 
 
 std::atomic<uint64_t> g_serial{1};
 
+bool is_logical(int op) { return op == PQG_FILTER_AND || op == PQG_FILTER_OR; }
+
+// The leftmost CONTAINS of the subtree at `i` in visiting order (left before right), -1 without one.
+int first_contains(const pqg_filter_node* n, int i) {
+  const int op = n[i].op;
+  if (op == PQG_FILTER_CONTAINS) return i;
+  if (is_leaf(op)) return -1;
+  const int l = first_contains(n, n[i].left);
+  if (l >= 0 || op == PQG_FILTER_NOT) return l;
+  return first_contains(n, n[i].right);
+}
+
+// LogicalInverseRewriter on a tree with contains: not(p) is LogicalInverter.invert(rewrite(p)), and
+// LogicalInverter.visit(Contains) throws (LogicalInverter.java:97-99). The walk is the rewriter's:
+// operands first, left before right, so the innermost not() above a contains throws, at the first
+// contains its inversion meets. Returns that node, -1 when nothing is refused.
+int inverse_refusal(const pqg_filter_node* n, int i) {
+  const int op = n[i].op;
+  if (is_leaf(op) || op == PQG_FILTER_CONTAINS) return -1;
+  const int l = inverse_refusal(n, n[i].left);
+  if (l >= 0) return l;
+  if (op == PQG_FILTER_NOT) return first_contains(n, n[i].left);
+  return inverse_refusal(n, n[i].right);
+}
+
+// ContainsRewriter.visit(And) / visit(Or) (ContainsRewriter.java:100-168) on the NOT-free program, restated
+// with its quirks: a side that is neither and / or nor a Contains returns the node as it is at once; the
+// sides are visited left first; a left side that became a Contains needs a Contains on the right
+// (UnsupportedOperationException), on the same column (ContainsComposedPredicate, IllegalArgumentException).
+// Returns the column of the Contains node `i` rewrites to, -1 when it stays an and / or. *code != PQG_OK:
+// refused at program node *bad.
+int contains_rewrite(const std::vector<pqg_filter_node>& p, int i, int* code, int* bad) {
+  int col[2] = {-1, -1};
+  for (int k = 0; k < 2; k++) {
+    const int c = k ? p[(size_t)i].right : p[(size_t)i].left;
+    const int op = p[(size_t)c].op;
+    if (is_logical(op)) {
+      col[k] = contains_rewrite(p, c, code, bad);
+      if (*code != PQG_OK) return -1;
+    } else if (op == PQG_FILTER_CONTAINS) {
+      col[k] = p[(size_t)p[(size_t)c].left].column;
+    } else {
+      return -1;
+    }
+  }
+  if (col[0] < 0) return -1;
+  if (col[1] < 0 || col[0] != col[1]) {
+    *code = col[1] < 0 ? PQG_ERR_UNSUPPORTED : PQG_ERR_INVALID_ARG;
+    *bad = i;
+    return -1;
+  }
+  return col[0];
+}
+
 }  // namespace
 
 extern "C" {
@@ -76,16 +131,23 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
   std::vector<int> uses((size_t)n_nodes, 0);
   for (int i = 0; i < n_nodes; i++) {
     const pqg_filter_node& nd = nodes[i];
-    if (nd.op < PQG_FILTER_EQ || nd.op > PQG_FILTER_NOT) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown op");
+    if (nd.op < PQG_FILTER_EQ || nd.op > PQG_FILTER_CONTAINS) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown op");
     if (nd.flags & ~(uint32_t)(PQG_FILTER_NULL_LITERAL | PQG_FILTER_UNSIGNED))
       return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown flags");
     if (!is_leaf(nd.op)) {
-      const bool two = nd.op != PQG_FILTER_NOT;
+      const bool two = is_logical(nd.op);
       if (nd.left < 0 || nd.left >= i) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: child index not below its parent");
       if (two ? (nd.right < 0 || nd.right >= i || nd.right == nd.left) : nd.right != -1)
         return fail(st, PQG_ERR_INVALID_ARG, i, "filter: child index not below its parent");
       uses[(size_t)nd.left]++;
       if (two) uses[(size_t)nd.right]++;
+      if (nd.op == PQG_FILTER_CONTAINS) {
+        // FilterApi.contains takes a SingleColumnFilterPredicate, without null among its values
+        if (nd.flags || nd.n_literals) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: contains with flags or literals of its own");
+        if (!is_leaf(nodes[nd.left].op)) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: contains of a node that is not a leaf");
+        if (nodes[nd.left].flags & PQG_FILTER_NULL_LITERAL)
+          return fail(st, PQG_ERR_INVALID_ARG, i, "filter: contains does not support null element values");
+      }
       continue;
     }
     if (nd.left != -1 || nd.right != -1) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: a leaf has children");
@@ -118,14 +180,18 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
 
   // ---- LogicalInverseRewriter -------------------------------------------------------
   // not(p) is invert(rewrite(p)); inverting twice is the identity on every node kind here, so a node
-  // ends up inverted when an odd number of NOTs stand above it.
+  // ends up inverted when an odd number of NOTs stand above it. A contains cannot be inverted at all.
+  {
+    const int bad = inverse_refusal(nodes, n_nodes - 1);
+    if (bad >= 0) return fail(st, PQG_ERR_UNSUPPORTED, bad, "filter: not() above a contains (Contains not supported yet)");
+  }
   std::vector<char> inv((size_t)n_nodes, 0);
   std::vector<int> remap((size_t)n_nodes, -1);
   for (int i = n_nodes - 1; i >= 0; i--) {
     const pqg_filter_node& nd = nodes[i];
     if (nd.op == PQG_FILTER_NOT) {
       inv[(size_t)nd.left] = !inv[(size_t)i];
-    } else if (!is_leaf(nd.op)) {
+    } else if (is_logical(nd.op)) {
       inv[(size_t)nd.left] = inv[(size_t)nd.right] = inv[(size_t)i];
     }
   }
@@ -134,12 +200,14 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
   f->serial = g_serial.fetch_add(1);
   f->column_types.assign(column_types, column_types + n_cols);
   if (n_literal_bytes) f->bytes.assign(literal_bytes, literal_bytes + n_literal_bytes);
+  std::vector<int> orig;  // program node -> input node
   for (int i = 0; i < n_nodes; i++) {
     pqg_filter_node nd = nodes[i];
     if (nd.op == PQG_FILTER_NOT) {
       remap[(size_t)i] = remap[(size_t)nd.left];
       continue;
     }
+    orig.push_back(i);
     if (inv[(size_t)i]) nd.op = inverse(nd.op);
     nd.reserved = 0;
     if (is_leaf(nd.op)) {
@@ -152,8 +220,9 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
       }
     } else {
       nd.left = remap[(size_t)nd.left];
-      nd.right = remap[(size_t)nd.right];
+      nd.right = is_logical(nd.op) ? remap[(size_t)nd.right] : -1;
       nd.column = -1;
+      if (nd.op == PQG_FILTER_CONTAINS) f->has_contains = true;
       nd.literal_begin = nd.n_literals = 0;
     }
     remap[(size_t)i] = (int)f->program.size();
@@ -162,6 +231,19 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
   if (f->program.size() > PQG_FILTER_MAX_NODES || f->cells.size() > PQG_FILTER_MAX_LITERALS) {
     delete f;
     return fail(st, PQG_ERR_UNSUPPORTED, -1, "filter: more than 64 nodes or 4096 literal cells after the rewrite");
+  }
+
+  // ---- ContainsRewriter's refusals (its merging is an optimisation: and / or stay as they are) ----
+  if (f->has_contains && is_logical(f->program.back().op)) {
+    int code = PQG_OK, bad = -1;
+    (void)contains_rewrite(f->program, (int)f->program.size() - 1, &code, &bad);
+    if (code != PQG_OK) {
+      const int node = orig[(size_t)bad];
+      delete f;
+      return fail(st, code, node,
+                  code == PQG_ERR_UNSUPPORTED ? "filter: Contains predicates cannot be composed with non-Contains predicates"
+                                              : "filter: composed Contains predicates must reference the same column");
+    }
   }
 
   // ---- sets for the binary search, slots, device image ----------------------------------
@@ -200,11 +282,14 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
       const pqg_filter_node& nd = f->program[i];
       if (is_leaf(nd.op) && nd.column == f->slot_column[s]) order[h.n_leaves++] = (uint8_t)i;
     }
+  std::vector<char> contained(h.n_nodes, 0);
+  for (const pqg_filter_node& nd : f->program)
+    if (nd.op == PQG_FILTER_CONTAINS) contained[(size_t)nd.left] = 1;
   for (uint32_t i = 0; i < h.n_nodes; i++) {
     const pqg_filter_node& nd = f->program[i];
     pqg::FilterDevNode d{};
     d.op = (uint8_t)nd.op;
-    d.flags = (uint8_t)nd.flags;
+    d.flags = (uint8_t)(nd.flags | (contained[i] ? pqg::FILTER_DEV_CONTAINED : 0u));
     if (is_leaf(nd.op)) {
       const int type = f->column_types[(size_t)nd.column];
       d.type = (uint8_t)type;
@@ -220,7 +305,7 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
       }
     } else {
       d.left = (uint8_t)nd.left;
-      d.right = (uint8_t)nd.right;
+      d.right = (uint8_t)(nd.right < 0 ? 0 : nd.right);
     }
     memcpy(img + sizeof(h) + i * sizeof(d), &d, sizeof(d));
   }
@@ -248,11 +333,12 @@ int pqg_filter_destroy(pqg_filter* filter) {
 
 namespace pqg {
 
-int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const pqg_filter_dictionary* dicts, int n_cols,
-                uint64_t n_rows, FilterCols* fc, FilterDictTab* dt, bool* any_dict) {
+// filter_bind and filter_bind_records: column `col` is at cols + col * stride (a pqg_filter_column, or the one
+// that begins a pqg_filter_record_column); repeated[col] != 0 (records only): a present repeated column.
+static int bind_slots(const pqg_filter* filter, const uint8_t* cols_base, size_t stride, const uint8_t* repeated,
+                      const pqg_filter_dictionary* dicts, uint64_t n_rows, FilterCols* fc, FilterDictTab* dt,
+                      bool* any_dict) {
   if (any_dict) *any_dict = false;
-  if (!filter || !fc || n_cols != (int)filter->column_types.size() || (n_cols > 0 && !cols)) return PQG_ERR_INVALID_ARG;
-  if (dicts && !dt) return PQG_ERR_INVALID_ARG;
   memset(fc, 0, sizeof(*fc));
   if (dt) {
     memset(dt, 0, sizeof(*dt));
@@ -262,7 +348,7 @@ int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const p
   fc->n_slots = (uint32_t)filter->slot_column.size();
   for (uint32_t s = 0; s < fc->n_slots; s++) {
     const int col = filter->slot_column[s];
-    const pqg_filter_column& c = cols[col];
+    const pqg_filter_column& c = *(const pqg_filter_column*)(cols_base + (size_t)col * stride);
     if (c.physical_type != filter->column_types[(size_t)col] || c.max_def < 0 || c.max_def > 254) return PQG_ERR_INVALID_ARG;
     const bool missing = c.max_def > 0 && !c.def_levels;
     const pqg_filter_dictionary* dc = dicts && dicts[col].values ? &dicts[col] : nullptr;
@@ -293,7 +379,9 @@ int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const p
     d.max_def = c.max_def;
     d.column = col;
     d.null_idx = -1;
-    if (d.dl) {
+    if (repeated && repeated[col]) {
+      d.null_idx = FILTER_NULL_IDX_REPEATED;
+    } else if (d.dl) {
       d.null_idx = (int32_t)fc->n_nullable;
       fc->null_slot[fc->n_nullable++] = (uint8_t)s;
     }
@@ -316,6 +404,95 @@ int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const p
     dt->in_lds = dt->table_words && dt->table_words * 8 <= PQG_FILTER_DICT_LDS_BYTES;
   }
   if (any_dict) *any_dict = any;
+  return PQG_OK;
+}
+
+int filter_bind(const pqg_filter* filter, const pqg_filter_column* cols, const pqg_filter_dictionary* dicts, int n_cols,
+                uint64_t n_rows, FilterCols* fc, FilterDictTab* dt, bool* any_dict) {
+  if (any_dict) *any_dict = false;
+  if (!filter || !fc || n_cols != (int)filter->column_types.size() || (n_cols > 0 && !cols)) return PQG_ERR_INVALID_ARG;
+  if (dicts && !dt) return PQG_ERR_INVALID_ARG;
+  // no repetition levels here: the reference refuses contains on a column with maxRepetitionLevel == 0
+  if (filter->has_contains) return PQG_ERR_INVALID_ARG;
+  return bind_slots(filter, (const uint8_t*)cols, sizeof(pqg_filter_column), nullptr, dicts, n_rows, fc, dt, any_dict);
+}
+
+int filter_bind_records(const pqg_filter* filter, const pqg_filter_record_column* cols, const pqg_filter_dictionary* dicts,
+                        int n_cols, uint64_t n_rows, FilterCols* fc, FilterDictTab* dt, bool* any_dict, FilterRecTab* rt) {
+  if (any_dict) *any_dict = false;
+  if (!filter || !fc || !dt || !rt || n_cols != (int)filter->column_types.size() || (n_cols > 0 && !cols))
+    return PQG_ERR_INVALID_ARG;
+  memset(rt, 0, sizeof(*rt));
+  memset(rt->leaf_rep, FILTER_NO_LEAF, sizeof(rt->leaf_rep));
+  memset(rt->node_leaf, FILTER_NO_LEAF, sizeof(rt->node_leaf));
+  // the structural rules of pqg_take_record_column, on the columns the predicate names (the others are not
+  // read); a missing column is exempt
+  std::vector<uint8_t> repeated((size_t)n_cols, 0), missing((size_t)n_cols, 0);
+  for (const int col : filter->slot_column) {
+    const pqg_filter_record_column& r = cols[col];
+    if (r.col.max_def > 0 && !r.col.def_levels) {
+      missing[(size_t)col] = 1;
+      continue;
+    }
+    if (r.max_rep < 0 || r.max_rep > 254 || r.reserved) return PQG_ERR_INVALID_ARG;
+    if (r.max_rep > 0) {
+      // a repeated node always adds a definition level
+      if (r.col.max_def == 0 || !r.rep_levels || r.n_slots < n_rows) return PQG_ERR_INVALID_ARG;
+      repeated[(size_t)col] = 1;
+    } else if (r.rep_levels || r.n_slots != n_rows) {
+      return PQG_ERR_INVALID_ARG;
+    }
+  }
+  // contains needs maxRepetitionLevel > 0, every other predicate a flat column
+  // (SchemaCompatibilityValidator.java:177-214)
+  std::vector<char> contained(filter->program.size(), 0);
+  for (const pqg_filter_node& nd : filter->program)
+    if (nd.op == PQG_FILTER_CONTAINS) contained[(size_t)nd.left] = 1;
+  for (size_t i = 0; i < filter->program.size(); i++) {
+    const pqg_filter_node& nd = filter->program[i];
+    if (!is_leaf(nd.op) || missing[(size_t)nd.column]) continue;
+    if ((contained[i] != 0) != (repeated[(size_t)nd.column] != 0)) return PQG_ERR_INVALID_ARG;
+  }
+  const int rc = bind_slots(filter, (const uint8_t*)cols, sizeof(pqg_filter_record_column), repeated.data(), dicts, n_rows,
+                            fc, dt, any_dict);
+  if (rc != PQG_OK) return rc;
+  rt->bitmap_words = (n_rows + PQG_FILTER_TILE_ROWS - 1) / PQG_FILTER_TILE_ROWS * (PQG_FILTER_TILE_ROWS / 64);
+  uint8_t slot_rep[PQG_FILTER_MAX_NODES];
+  for (uint32_t s = 0; s < fc->n_slots; s++) {
+    const int col = filter->slot_column[s];
+    slot_rep[s] = FILTER_NO_LEAF;
+    if (!repeated[(size_t)col]) continue;
+    slot_rep[s] = (uint8_t)rt->n_rep;
+    rt->rep_slot[rt->n_rep] = (uint8_t)s;
+    rt->rl[rt->n_rep] = cols[col].rep_levels;
+    rt->n_slots[rt->n_rep] = cols[col].n_slots;
+    if (cols[col].n_slots > rt->max_slots) rt->max_slots = cols[col].n_slots;
+    rt->n_rep++;
+  }
+  for (size_t i = 0; i < filter->program.size(); i++) {
+    const pqg_filter_node& nd = filter->program[i];
+    if (nd.op != PQG_FILTER_CONTAINS) continue;
+    const int col = filter->program[(size_t)nd.left].column;
+    const size_t s = (size_t)(std::find(filter->slot_column.begin(), filter->slot_column.end(), col) - filter->slot_column.begin());
+    rt->node_leaf[i] = (uint8_t)rt->n_leaves;
+    rt->leaf_node[rt->n_leaves] = (uint8_t)nd.left;
+    rt->leaf_rep[rt->n_leaves] = slot_rep[s];
+    rt->n_leaves++;
+  }
+  // a column's contains leaves share its loads: groups of up to FILTER_CONTAINS_GROUP
+  for (uint32_t ri = 0; ri < rt->n_rep; ri++) {
+    uint32_t in_group = FILTER_CONTAINS_GROUP;  // the next leaf opens a group
+    for (uint32_t li = 0; li < rt->n_leaves; li++) {
+      if (rt->leaf_rep[li] != ri) continue;
+      if (in_group == FILTER_CONTAINS_GROUP) {
+        rt->group_rep[rt->n_groups] = (uint8_t)ri;
+        rt->n_groups++;
+        in_group = 0;
+      }
+      rt->group_leaf[rt->n_groups - 1][in_group++] = (uint8_t)li;
+      rt->group_n[rt->n_groups - 1] = (uint8_t)in_group;
+    }
+  }
   return PQG_OK;
 }
 

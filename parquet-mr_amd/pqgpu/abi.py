@@ -233,7 +233,7 @@ FILTER_MAX_LITERALS = 4096       # literal cells
 FILTER_MAX_LITERAL_BYTES = 16384  # BYTE_ARRAY literal bytes
 # pqg_filter_op
 (FILTER_EQ, FILTER_NOTEQ, FILTER_LT, FILTER_LTEQ, FILTER_GT, FILTER_GTEQ, FILTER_IN, FILTER_NOTIN, FILTER_AND,
- FILTER_OR, FILTER_NOT) = range(11)
+ FILTER_OR, FILTER_NOT, FILTER_CONTAINS) = range(12)
 FILTER_NULL_LITERAL = 1  # pqg_filter_node.flags: the literal is null / the set contains null
 FILTER_UNSIGNED = 2      # pqg_filter_node.flags: UINT_32 / UINT_64 order
 
@@ -268,6 +268,15 @@ class FilterDictionary(C.Structure):
 
 
 assert C.sizeof(FilterDictionary) == 24
+
+
+class FilterRecordColumn(C.Structure):
+    """pqg_filter_record_column (64 bytes): a pqg_filter_column plus the column's repetition levels."""
+    _fields_ = [("col", FilterColumn), ("max_rep", C.c_int32), ("reserved", C.c_int32), ("rep_levels", C.c_void_p),
+                ("n_slots", C.c_uint64)]
+
+
+assert C.sizeof(FilterRecordColumn) == 64
 
 
 # ---- row selection (include/pqgpu.h, "row selection") -----------------------------------------------

@@ -639,6 +639,54 @@ class Decoder:
         sel._keep = (flt, cols, [getattr(c, "dictionary", None) for c in cols])
         return sel
 
+    def filter_records(self, pred, cols, n_rows, row_ids=True, capacity=None, out=None):
+        """Decoder.filter over records (pqg_filter_run_records): `n_rows` counts records, `cols` may hold
+        repeated DeviceColumns (rep_levels, def_levels, n_slots, max_rep as decode() left them), and the
+        predicate reaches them through filter.contains(leaf): the records one of whose list elements
+        satisfies the leaf. Flat columns, MissingColumns, dictionaries and the outputs are as for
+        filter(); the Selection goes straight into take_records()."""
+        from . import filter as F
+        flt = pred if isinstance(pred, F.Filter) else F.Filter(pred, cols)
+        n_words = (n_rows + 63) // 64
+        capacity = n_rows if capacity is None else int(capacity)
+        if out is not None:
+            words, ids, result = out
+        else:
+            words = torch.empty(max(n_words, 1), dtype=torch.int64, device=self.device)
+            ids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self.device) if row_ids else None
+            result = torch.empty(16, dtype=torch.uint8, device=self.device)
+        arr = (abi.FilterRecordColumn * max(1, len(cols)))()
+        dicts = None
+        for i, c in enumerate(cols):
+            d = getattr(c, "dictionary", None) if getattr(c, "flags", 0) & abi.COLUMN_DICTIONARY_IDS else None
+            if d is not None:
+                if dicts is None:
+                    dicts = (abi.FilterDictionary * len(cols))()
+                dicts[i].values = d.values.data_ptr()
+                dicts[i].binary_data = d.binary_data.data_ptr() if d.binary_data is not None else None
+                dicts[i].n_entries = d.n_values
+            a = arr[i].col
+            a.physical_type = c.physical_type if d is None else d.physical_type
+            a.max_def = c.max_def
+            a.values = c.values.data_ptr() if c.values is not None else None
+            a.binary_data = c.binary_data.data_ptr() if c.binary_data is not None else None
+            a.def_levels = c.def_levels.data_ptr() if c.def_levels is not None else None
+            a.n_values = c.n_values
+            rl = getattr(c, "rep_levels", None)
+            arr[i].max_rep = int(getattr(c, "max_rep", 0) or 0)
+            arr[i].rep_levels = rl.data_ptr() if rl is not None and arr[i].max_rep > 0 else None
+            ns = getattr(c, "n_slots", None)
+            arr[i].n_slots = n_rows if ns is None else int(ns)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))  # allocations / fills first
+        rc = native.lib().pqg_filter_run_records(
+            self.ctx, flt.handle, C.addressof(arr), C.addressof(dicts) if dicts is not None else None, len(cols), n_rows,
+            words.data_ptr(), ids.data_ptr() if ids is not None else None, capacity if ids is not None else 0,
+            result.data_ptr())
+        native.check(rc, what="pqg_filter_run_records")
+        sel = F.Selection(self, n_rows, words[:n_words], ids, result, capacity)
+        sel._keep = (flt, cols, [getattr(c, "dictionary", None) for c in cols])
+        return sel
+
     # -- row selection ----------------------------------------------------------------
     def take(self, selection, cols, n_rows=None, rows_capacity=None, out=None):
         """Gather the rows a selection keeps into compact columns (pqg_take): what

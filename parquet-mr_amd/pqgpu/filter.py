@@ -7,6 +7,7 @@ A small predicate DSL named after parquet-mr's FilterApi (filter2/predicate/Filt
     sel = decoder.filter(pred, cols, n_rows)      # cols: the DeviceColumns decode() returned
     sel.count, sel.bitmap, sel.row_ids
 
+`contains(leaf)` is FilterApi.contains on a repeated column: Decoder.filter_records evaluates it per record.
 `None` is the null literal (eq / not_eq, or a member of an in_ / not_in set). `compile` flattens a
 predicate to the node, literal and byte tables of the C ABI; `Filter` is the created pqg_filter
 (validated and rewritten without not(), as FilterCompat.get does with LogicalInverseRewriter).
@@ -20,7 +21,7 @@ from . import abi, native
 _LEAF_OPS = {"eq": abi.FILTER_EQ, "not_eq": abi.FILTER_NOTEQ, "lt": abi.FILTER_LT, "lt_eq": abi.FILTER_LTEQ,
              "gt": abi.FILTER_GT, "gt_eq": abi.FILTER_GTEQ, "in": abi.FILTER_IN, "not_in": abi.FILTER_NOTIN}
 OP_NAMES = {v: k for k, v in _LEAF_OPS.items()}
-OP_NAMES.update({abi.FILTER_AND: "and", abi.FILTER_OR: "or", abi.FILTER_NOT: "not"})
+OP_NAMES.update({abi.FILTER_AND: "and", abi.FILTER_OR: "or", abi.FILTER_NOT: "not", abi.FILTER_CONTAINS: "contains"})
 
 
 class Column:
@@ -68,6 +69,12 @@ def not_in(column, values): return _leaf(abi.FILTER_NOTIN, column, tuple(values)
 def and_(left, right): return Predicate(abi.FILTER_AND, children=(left, right))
 def or_(left, right): return Predicate(abi.FILTER_OR, children=(left, right))
 def not_(pred): return Predicate(abi.FILTER_NOT, children=(pred,))
+
+
+def contains(leaf):
+    """FilterApi.contains: some element of the record's list satisfies `leaf` (eq .. not_in on a repeated
+    column; Decoder.filter_records evaluates it)."""
+    return Predicate(abi.FILTER_CONTAINS, children=(leaf,))
 
 
 def literal_cell(physical_type, value):

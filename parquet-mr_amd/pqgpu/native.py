@@ -34,6 +34,8 @@ EXPORTS = [
     "pqg_filter_create", "pqg_filter_program", "pqg_filter_destroy", "pqg_filter_run",
     # ... on dictionary-id columns, and the dictionary itself as a column
     "pqg_filter_run_dict", "pqg_decode_dictionary",
+    # ... on list columns: contains()
+    "pqg_filter_run_records",
     # row selection (the rows a bitmap keeps, as compact columns)
     "pqg_take",
     # ... with repeated columns: whole records
@@ -111,6 +113,7 @@ def lib():
         L.pqg_filter_destroy.argtypes = [vp]
         L.pqg_filter_run.argtypes = [vp, vp, vp, i32, u64, vp, vp, u64, vp]
         L.pqg_filter_run_dict.argtypes = [vp, vp, vp, vp, i32, u64, vp, vp, u64, vp]
+        L.pqg_filter_run_records.argtypes = [vp, vp, vp, vp, i32, u64, vp, vp, u64, vp]
         L.pqg_decode_dictionary.argtypes = [vp, vp, u64, vp, C.POINTER(abi.Status)]
         L.pqg_take.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
         L.pqg_take_records.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
