@@ -39,7 +39,9 @@
  * record filters on list columns (PQG_FILTER_CONTAINS, pqg_filter_record_column,
  * pqg_filter_run_records); record filters on dictionary-id columns (pqg_filter_dictionary, pqg_filter_run_dict,
  * PQG_FILTER_DICT_LDS_BYTES) and pqg_decode_dictionary; record selection on repeated columns
- * (pqg_take_record_column, pqg_take_record_counts, pqg_take_records).
+ * (pqg_take_record_column, pqg_take_record_counts, pqg_take_records); record filters on INT96 and
+ * FIXED_LEN_BYTE_ARRAY columns and the three binary comparators (pqg_filter_binary_order,
+ * pqg_filter_column_type, pqg_filter_create_typed).
  * ABI 5: record-level filter2 predicates over decoded columns (pqg_filter_create /
  * pqg_filter_program / pqg_filter_destroy on the host, pqg_filter_run on the device).
  * ABI 4: pqg_page_desc carries the V2 header's num_nulls
@@ -679,8 +681,9 @@ int pqg_pages_from_headers(const pqg_page_header* headers, int n_headers, int co
  * unsigned lexicographic bytes then length for BYTE_ARRAY. Null rows: eq / lt / ltEq / gt / gtEq / in
  * are false and notEq / notIn true; eq(c, null) holds on null rows only, notEq(c, null) on the others;
  * an in / notIn set containing null behaves as eq / notEq(c, null) (the reference ignores its other
- * members). PQG_ERR_UNSUPPORTED at creation: INT96 and FIXED_LEN_BYTE_ARRAY columns; programs over
- * the limits below. PQG_ERR_INVALID_ARG: lt / ltEq / gt / gtEq on BOOLEAN (IllegalArgumentException in
+ * members). PQG_ERR_UNSUPPORTED at creation: INT96 and FIXED_LEN_BYTE_ARRAY columns declared through
+ * pqg_filter_create's bare type array (pqg_filter_create_typed, below, declares their width and order,
+ * and the signed-integer order of a DECIMAL on BYTE_ARRAY); programs over the limits below. PQG_ERR_INVALID_ARG: lt / ltEq / gt / gtEq on BOOLEAN (IllegalArgumentException in
  * the reference) or against null, a malformed table. */
 #define PQG_FILTER_TILE_ROWS 4096          /* rows per device tile (one wave; a multiple of 64) */
 #define PQG_FILTER_MAX_NODES 64            /* nodes of the rewritten program */
@@ -730,6 +733,49 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
  * Writes min(cap, count) nodes and returns the count; -1 without a filter. */
 int pqg_filter_program(const pqg_filter* filter, pqg_filter_node* out, int cap);
 int pqg_filter_destroy(pqg_filter* filter);
+
+/* ---- binary comparators: DECIMAL, FIXED_LEN_BYTE_ARRAY, INT96, FLOAT16 (an addition to ABI 6) ----
+ * The reference compares a Binary column (BINARY, FIXED_LEN_BYTE_ARRAY, INT96) with one of three
+ * comparators, chosen by PrimitiveType.comparator() from the logical type
+ * (schema/PrimitiveType.java:239-413, schema/PrimitiveComparator.java:183-295):
+ *   UNSIGNED_BYTES   Binary.lexicographicCompare: BINARY / FLBA without annotation, STRING, ENUM, JSON,
+ *                    BSON, UUID, INTERVAL
+ *   SIGNED_INTEGER   big-endian two's complement, the shorter side padded with its own sign (an empty
+ *                    value is non-negative): DECIMAL on BINARY and on FLBA, and every INT96 column
+ *   FLOAT16          Float16.compare of the two little-endian bytes (every NaN one value above +Infinity,
+ *                    -0.0 below +0.0): FLOAT16 on FLBA(2)
+ * eq / notEq / in / notIn use the comparator too (compare(...) == 0): under SIGNED_INTEGER 00 94 equals
+ * 00 00 00 94, an empty literal equals every all-zero value, and in(c, {00 01}) matches a stored 01. */
+enum pqg_filter_binary_order {
+  PQG_FILTER_ORDER_UNSIGNED_BYTES = 0, /* Binary.lexicographicCompare: unsigned bytes, then length */
+  PQG_FILTER_ORDER_SIGNED_INTEGER = 1, /* big-endian two's complement; the shorter side padded with its sign */
+  PQG_FILTER_ORDER_FLOAT16 = 2         /* Float16.compare of the two little-endian bytes */
+};
+typedef struct pqg_filter_column_type { /* sizeof == 16 */
+  int32_t physical_type; /* pqg_physical_type */
+  int32_t type_length;   /* FIXED_LEN_BYTE_ARRAY: >= 1; INT96: 0 or 12; otherwise 0 */
+  int32_t binary_order;  /* pqg_filter_binary_order; 0 for the non-binary types */
+  int32_t reserved;      /* 0 */
+} pqg_filter_column_type;
+
+/* pqg_filter_create with a width and a comparator per column; pqg_filter_create is this function with
+ * type_length = 0 and binary_order = 0 in every column, plus its refusal of INT96 / FLBA columns.
+ * Literals of BYTE_ARRAY, FIXED_LEN_BYTE_ARRAY and INT96 columns are all BYTE_ARRAY cells
+ * (offset | length << 32 into literal_bytes) of any length, 0 included: the comparators define the
+ * result when it differs from the column's width. All eight leaf ops are valid on these columns.
+ * PQG_ERR_INVALID_ARG beyond pqg_filter_create's, value_index naming the node (for `reserved`, which is
+ * checked on every column, the column): non-zero reserved; type_length or binary_order set on a non-binary type;
+ * FLBA with type_length < 1; INT96 with a type_length other than 0 or 12, or an order other than
+ * SIGNED_INTEGER (the reference has no other comparator for it); FLOAT16 on anything but FLBA with
+ * type_length == 2, or with a literal whose length is not 2; PQG_FILTER_UNSIGNED on a binary column.
+ * At run time the column's physical_type must equal the declared one and the element width comes from
+ * the filter: values = n_values dense elements of 12 bytes (INT96, 4-byte aligned) or type_length bytes
+ * (FLBA, any alignment) as pqg_decode leaves them; a dictionary holds n_entries such elements. Every
+ * element load stays inside [values, values + n_values * width). pqg_filter_run, pqg_filter_run_dict and
+ * pqg_filter_run_records all take such filters. */
+int pqg_filter_create_typed(const pqg_filter_node* nodes, int n_nodes, const pqg_filter_column_type* columns,
+                            int n_cols, const uint64_t* literals, int n_literals, const uint8_t* literal_bytes,
+                            uint64_t n_literal_bytes, pqg_filter** out, pqg_status* st);
 
 /* One decoded column as pqg_decode left it. max_def == 0: a required column, row r is values[r].
  * max_def > 0: def_levels holds one byte per row and values the dense non-null values in row order;

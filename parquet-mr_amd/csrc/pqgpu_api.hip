@@ -1545,6 +1545,7 @@ static_assert(sizeof(pqg_filter_node) == 32 && sizeof(pqg_filter_column) == 40 &
 
 static_assert(sizeof(pqg_filter_dictionary) == 24, "filter dictionary ABI layout");
 static_assert(sizeof(pqg_filter_record_column) == 64, "filter record column ABI layout");
+static_assert(sizeof(pqg_filter_column_type) == 16, "filter column type ABI layout");
 
 // The launches of pqg_filter_run / pqg_filter_run_dict once pqg::filter_bind has accepted the columns, and
 // with `rec` (whose dt is `dt`) those of pqg_filter_run_records with contains leaves.
@@ -1591,13 +1592,13 @@ static int filter_launch(pqg_ctx* ctx, const pqg_filter* filter, const pqg::Filt
     const hipError_t e = pqg::launch_filter_records(
         ctx->stream, (const uint8_t*)ctx->filter_image.p, (uint32_t)filter->image.size(), fc, n_rows,
         (uint64_t*)ctx->filter_scratch.p, d_bitmap, d_row_ids, row_ids_capacity, d_result,
-        (const pqg::FilterRecDev*)ctx->filter_dict.p, rec);
+        (const pqg::FilterRecDev*)ctx->filter_dict.p, rec, filter->binary_paths);
     return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
   }
   const hipError_t e =
       pqg::launch_filter(ctx->stream, (const uint8_t*)ctx->filter_image.p, (uint32_t)filter->image.size(), fc, n_rows,
                          (uint64_t*)ctx->filter_scratch.p, d_bitmap, d_row_ids, row_ids_capacity, d_result,
-                         dt ? (const pqg::FilterDictTab*)ctx->filter_dict.p : nullptr, dt);
+                         dt ? (const pqg::FilterDictTab*)ctx->filter_dict.p : nullptr, dt, filter->binary_paths);
   return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
 }
 

@@ -12,7 +12,11 @@ namespace pqg {
 
 // One node of the device program (16 bytes). Leaves name a slot: the s-th distinct column the
 // program reads. Literal cells hold comparator keys (int64, compared signed) for the fixed-width
-// types and offset | length << 32 into the literal bytes for BYTE_ARRAY.
+// types and offset | length << 32 into the literal bytes for BYTE_ARRAY. The binary types (BYTE_ARRAY,
+// FIXED_LEN_BYTE_ARRAY, INT96) carry their comparator in the flags: none = unsigned bytes;
+// FILTER_DEV_FLOAT16: cells hold keys as for the fixed-width types; FILTER_DEV_SIGNED: big-endian two's
+// complement, and with FILTER_DEV_KEY128 every literal takes three cells: its BYTE_ARRAY cell, then the
+// high (signed) and low (unsigned) half of its sign-extended 128-bit value.
 struct FilterDevNode {
   uint8_t op;     // pqg_filter_op, never NOT
   uint8_t flags;  // PQG_FILTER_*
@@ -22,8 +26,12 @@ struct FilterDevNode {
   uint8_t right;
   uint16_t n_lit;
   uint32_t lit_begin;
-  uint32_t pad;
+  uint32_t width;  // leaves on INT96 / FIXED_LEN_BYTE_ARRAY: bytes per element; otherwise 0
 };
+constexpr uint8_t FILTER_DEV_SIGNED = 0x04;   // PQG_FILTER_ORDER_SIGNED_INTEGER
+constexpr uint8_t FILTER_DEV_FLOAT16 = 0x08;  // PQG_FILTER_ORDER_FLOAT16
+constexpr uint8_t FILTER_DEV_KEY128 = 0x10;   // with FILTER_DEV_SIGNED: literals carry 128-bit keys
+constexpr uint32_t FILTER_KEY128_BYTES = 16;  // the widest value the 128-bit keys compare
 
 // Header of the device image: FilterDevHeader, nodes[n_nodes], order[PQG_FILTER_MAX_NODES] (u8: the
 // leaves grouped by slot, then nothing), cells[n_cells] (8 bytes each), bytes[n_bytes] padded to 8 + 8.
@@ -130,6 +138,8 @@ struct pqg_filter {
   uint64_t serial = 0;                  // unique per created filter (the ctx caches the uploaded image by it)
   std::vector<pqg_filter_node> program; // rewritten, NOT-free, post-order; literal_begin into `cells`
   std::vector<int32_t> column_types;
+  std::vector<pqg_filter_column_type> columns;  // as declared (pqg_filter_create: width and order 0)
+  bool binary_paths = false;            // a leaf on INT96 / FLBA or with an order of its own: the kernels' BIN form
   std::vector<uint64_t> cells;          // raw literal cells, one private range per leaf (sets > 8 sorted)
   std::vector<uint8_t> bytes;           // BYTE_ARRAY literal bytes
   std::vector<int32_t> slot_column;     // slot -> column index
@@ -163,5 +173,32 @@ PQG_FILTER_HD inline int64_t filter_key(int type, bool is_unsigned, uint64_t raw
     }
     default: return 0;
   }
+}
+
+// Float16.compare (schema/Float16.java:108-134) as a key: every NaN is 0x7e00, above +Infinity (0x7c00);
+// a negative value of magnitude m is -m - 1, so -0.0 (-1) stands below +0.0 (0).
+PQG_FILTER_HD inline int64_t filter_key_float16(uint32_t bits) {
+  const uint32_t m = bits & 0x7FFFu;
+  if (m > 0x7C00u) return 0x7E00;
+  return (bits & 0x8000u) ? -(int64_t)m - 1 : (int64_t)m;
+}
+
+// The value of n big-endian two's-complement bytes as a sign-extended 128-bit integer (hi signed, lo
+// unsigned); an empty value is 0. Leading bytes that only repeat the sign are dropped first, which changes
+// no comparison of BINARY_AS_SIGNED_INTEGER_COMPARATOR (it pads the shorter side with exactly those bytes).
+// false: more than 16 bytes remain.
+inline bool filter_key128(const uint8_t* p, uint32_t n, int64_t* hi, uint64_t* lo) {
+  const bool neg = n > 0 && (p[0] & 0x80u);
+  const uint8_t pad = neg ? 0xFFu : 0u;
+  while (n > 1 && p[0] == pad && ((p[1] & 0x80u) != 0) == neg) p++, n--;
+  if (n > FILTER_KEY128_BYTES) return false;
+  uint64_t h = neg ? ~0ull : 0ull, l = h;
+  for (uint32_t i = 0; i < n; i++) {
+    h = (h << 8) | (l >> 56);
+    l = (l << 8) | p[i];
+  }
+  *hi = (int64_t)h;
+  *lo = l;
+  return true;
 }
 }  // namespace pqg

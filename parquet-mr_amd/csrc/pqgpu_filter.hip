@@ -14,6 +14,9 @@
 // With dictionary-id columns (pqg_filter_run_dict) one launch goes first when a leaf has a verdict table:
 //   k_filter_dict  one wave per 64 entries of a leaf's dictionary: the leaf on every entry, one bit each
 // and k_filter_eval<true> takes a leaf's verdict on such a column as bit `id` of its table.
+// BIN: a program with a leaf on an INT96 / FIXED_LEN_BYTE_ARRAY column or under the signed-integer or FLOAT16
+// order runs the *_bin form of k_filter_dict, k_filter_eval, k_filter_eval_records and k_filter_contains:
+// the same code with those paths compiled in. Every other program runs the kernels without them.
 #include "pqgpu_device.h"
 #include "pqgpu_filter.h"
 
@@ -108,7 +111,8 @@ __global__ __launch_bounds__(256) void k_filter_scan(uint64_t* __restrict__ arr,
 // BYTE_ARRAY value's bytes are.
 struct LaneValue {
   int64_t key;
-  rsrc_t rs;             // BYTE_ARRAY: the binary data from the wave's first value on (range-checked)
+  uint64_t lo;           // FILTER_DEV_KEY128: the value is key (high, signed) : lo
+  rsrc_t rs;             // binary types: the data from the wave's first value on (range-checked)
   uint32_t rel, len;     // the value's bytes are [rel, rel + len) of rs
   const uint8_t* slow;   // non-null: the value's bytes start here and do not fit rs (over 4 GiB away): plain loads
 };
@@ -137,10 +141,106 @@ __device__ __forceinline__ int compare_bytes(const LaneValue& v, const uint8_t* 
   return v.len < llen ? -1 : (v.len > llen ? 1 : 0);
 }
 
-// compare(value, literal cell j) of the column's PrimitiveComparator.
-__device__ __forceinline__ int compare_cell(const LaneValue& v, bool binary, const uint64_t* cells, const uint8_t* lbytes,
-                                            uint32_t j) {
-  const uint64_t cell = cells[j];
+__device__ __forceinline__ uint32_t lds_dword(const uint8_t* p) {  // any alignment; the image is padded behind its bytes
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// Unsigned order of the value's bytes [pv, pv + n) against n bytes of the other side, of which other(p) gives
+// 4 at p (little endian; bytes past n unspecified).
+template <class F>
+__device__ __forceinline__ int compare_span(const LaneValue& v, uint32_t pv, uint32_t n, F other) {
+  for (uint32_t p = 0; p < n; p += 4) {
+    uint32_t a = value_dword(v, pv + p), b = other(p);
+    const uint32_t rem = n - p;
+    const uint32_t m = rem >= 4 ? 0xFFFFFFFFu : (1u << (8u * rem)) - 1u;
+    a &= m;
+    b &= m;
+    if (a != b) return __builtin_bswap32(a) < __builtin_bswap32(b) ? -1 : 1;
+  }
+  return 0;
+}
+
+// BINARY_AS_SIGNED_INTEGER_COMPARATOR (PrimitiveComparator.java:214-279) of the lane's value with the literal
+// at lit[0, llen), byte-wise for any lengths: the signs (first bytes; an empty side is non-negative), the
+// longer side's extra leading bytes against the shorter side's sign padding, the common tail unsigned.
+__device__ __forceinline__ int compare_signed_bytes(const LaneValue& v, const uint8_t* lit, uint32_t llen) {
+  const bool neg_v = v.len != 0 && (value_dword(v, 0) & 0x80u) != 0;
+  const bool neg_l = llen != 0 && (lit[0] & 0x80u) != 0;
+  if (neg_v != neg_l) return neg_v ? -1 : 1;
+  const uint32_t pad = neg_v ? 0xFFFFFFFFu : 0u;
+  uint32_t pv = 0;
+  if (v.len < llen) {
+    const uint32_t d = llen - v.len;
+    for (uint32_t p = 0; p < d; p += 4) {
+      const uint32_t m = d - p >= 4 ? 0xFFFFFFFFu : (1u << (8u * (d - p))) - 1u;
+      const uint32_t a = pad & m, b = lds_dword(lit + p) & m;
+      if (a != b) return __builtin_bswap32(a) < __builtin_bswap32(b) ? -1 : 1;
+    }
+    lit += d;
+    llen = v.len;
+  } else if (v.len > llen) {
+    pv = v.len - llen;
+    const int c = compare_span(v, 0, pv, [pad](uint32_t) { return pad; });
+    if (c) return c;
+  }
+  return compare_span(v, pv, llen, [lit](uint32_t p) { return lds_dword(lit + p); });
+}
+
+// The lane's value of at most FILTER_KEY128_BYTES big-endian two's-complement bytes as a sign-extended
+// 128-bit integer: up to four dwords, byte-swapped into one 128-bit word whose top bytes are the value,
+// shifted down arithmetically (what was loaded past the value leaves with the shift). Empty: 0.
+// A value inside the wave's buffer takes the five aligned dwords that cover any 16 bytes and v_alignbyte
+// (value_dword would fetch eight); a dword past the buffer reads 0.
+__device__ __forceinline__ void value_key128(const LaneValue& v, int64_t* hi, uint64_t* lo) {
+  uint32_t c[4];
+  if (!v.slow) {
+    const uint32_t a = v.rel & ~3u, sb = v.rel & 3u;
+    uint32_t w[5];
+#pragma unroll
+    for (uint32_t k = 0; k < 5; k++) w[k] = ld32(v.rs, a + 4u * k);
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) c[k] = __builtin_bswap32(__builtin_amdgcn_alignbyte(w[k + 1], w[k], sb));
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) c[k] = 4u * k < v.len ? __builtin_bswap32(value_dword(v, 4u * k)) : 0u;
+  }
+  int64_t h = (int64_t)(((uint64_t)c[0] << 32) | c[1]);
+  uint64_t l = ((uint64_t)c[2] << 32) | c[3];
+  const uint32_t sh = 8u * (FILTER_KEY128_BYTES - v.len);
+  if (sh >= 128u) {
+    h = 0;
+    l = 0;
+  } else if (sh >= 64u) {
+    l = (uint64_t)(h >> (sh - 64u));
+    h >>= 63;
+  } else if (sh) {
+    l = (l >> sh) | ((uint64_t)h << (64u - sh));
+    h >>= sh;
+  }
+  *hi = h;
+  *lo = l;
+}
+
+__device__ __forceinline__ bool binary_type(int32_t type) {
+  return type == PQG_BYTE_ARRAY || type == PQG_INT96 || type == PQG_FIXED_LEN_BYTE_ARRAY;
+}
+
+// compare(value, literal j of the leaf whose cells begin at `b`) of the column's PrimitiveComparator.
+template <bool BIN>
+__device__ __forceinline__ int compare_cell(const LaneValue& v, bool binary, uint32_t flags, const uint64_t* cells,
+                                            const uint8_t* lbytes, uint32_t b, uint32_t j) {
+  if (BIN && (flags & FILTER_DEV_SIGNED)) {
+    const bool keys = (flags & FILTER_DEV_KEY128) != 0;
+    const uint64_t* c = cells + b + (keys ? 3u * j : j);
+    if (keys && v.len <= FILTER_KEY128_BYTES) {  // leaf_value made the value's key
+      const int64_t hi = (int64_t)c[1];
+      const uint64_t lo = c[2];
+      if (v.key != hi) return v.key < hi ? -1 : 1;
+      return (v.lo > lo) - (v.lo < lo);
+    }
+    return compare_signed_bytes(v, lbytes + (uint32_t)c[0], (uint32_t)(c[0] >> 32));
+  }
+  const uint64_t cell = cells[b + j];
   if (!binary) {
     const int64_t k = (int64_t)cell;
     return (v.key > k) - (v.key < k);
@@ -148,11 +248,29 @@ __device__ __forceinline__ int compare_cell(const LaneValue& v, bool binary, con
   return compare_bytes(v, lbytes + (uint32_t)cell, (uint32_t)(cell >> 32));
 }
 
+// The value a leaf compares, from the column's loaded value: the comparator key of a fixed-width value
+// (the unsigned flag is the leaf's), of a FLOAT16, or of a signed integer that the 128-bit keys cover.
+template <bool BIN>
+__device__ __forceinline__ LaneValue leaf_value(const FilterDevNode& nd, int32_t type, bool valid, const LaneValue& v) {
+  LaneValue lv = v;
+  if (BIN && binary_type(type)) {
+    if (nd.flags & FILTER_DEV_FLOAT16)
+      lv.key = valid ? filter_key_float16(value_dword(v, 0) & 0xFFFFu) : 0;
+    else if ((nd.flags & FILTER_DEV_KEY128) && valid && v.len <= FILTER_KEY128_BYTES)
+      value_key128(v, &lv.key, &lv.lo);
+    return lv;
+  }
+  if (type != PQG_BYTE_ARRAY) lv.key = filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, (uint64_t)v.key);
+  return lv;
+}
+
 // One leaf on one row (the generated ValueInspectors): `valid` = the row has a value.
+template <bool BIN>
 __device__ __forceinline__ bool leaf_eval(const FilterDevNode& nd, bool valid, const LaneValue& v, const uint64_t* cells,
                                           const uint8_t* lbytes) {
   const bool null_lit = (nd.flags & PQG_FILTER_NULL_LITERAL) != 0;
-  const bool binary = nd.type == PQG_BYTE_ARRAY;
+  const bool binary = BIN ? binary_type(nd.type) && !(nd.flags & FILTER_DEV_FLOAT16) : nd.type == PQG_BYTE_ARRAY;
+  const uint32_t fl = nd.flags;
   const uint32_t b = nd.lit_begin, n = nd.n_lit;
   if (null_lit)  // eq(c, null) / in(c, {null, ...}): null rows; notEq / notIn: the others
     return (nd.op == PQG_FILTER_EQ || nd.op == PQG_FILTER_IN) ? !valid : valid;
@@ -160,12 +278,12 @@ __device__ __forceinline__ bool leaf_eval(const FilterDevNode& nd, bool valid, c
     bool found = false;
     if (valid) {
       if (n <= FILTER_IN_LINEAR) {
-        for (uint32_t j = 0; j < n; j++) found |= compare_cell(v, binary, cells, lbytes, b + j) == 0;
+        for (uint32_t j = 0; j < n; j++) found |= compare_cell<BIN>(v, binary, fl, cells, lbytes, b, j) == 0;
       } else {  // the set is sorted by comparator order
         uint32_t lo = 0, hi = n;
         while (lo < hi) {
           const uint32_t mid = (lo + hi) >> 1;
-          const int c = compare_cell(v, binary, cells, lbytes, b + mid);
+          const int c = compare_cell<BIN>(v, binary, fl, cells, lbytes, b, mid);
           if (c == 0) {
             found = true;
             break;
@@ -176,7 +294,7 @@ __device__ __forceinline__ bool leaf_eval(const FilterDevNode& nd, bool valid, c
     }
     return nd.op == PQG_FILTER_IN ? found : !found;
   }
-  const int c = valid ? compare_cell(v, binary, cells, lbytes, b) : 0;
+  const int c = valid ? compare_cell<BIN>(v, binary, fl, cells, lbytes, b, 0) : 0;
   switch (nd.op) {
     case PQG_FILTER_EQ: return valid && c == 0;
     case PQG_FILTER_NOTEQ: return !valid || c != 0;
@@ -190,17 +308,27 @@ __device__ __forceinline__ bool leaf_eval(const FilterDevNode& nd, bool valid, c
 // The lane's value `idx` of a column (`valid` lanes only; the whole wave calls): the raw bits of a fixed-width
 // value (the key is per leaf), or where a BYTE_ARRAY value's bytes are. ENTRY: the column is a dictionary of
 // n_values entries, whose offsets are clamped into [offsets[0], offsets[n_values]] (n_values > 0).
-template <bool ENTRY>
-__device__ __forceinline__ LaneValue load_value(int32_t type, const void* values, const uint8_t* binary, bool valid,
-                                                uint64_t idx, uint64_t n_values) {
+// BIN: an INT96 / FIXED_LEN_BYTE_ARRAY value is the `width` bytes at idx * width of `values`, found like a
+// BYTE_ARRAY value's (idx < n_values: inside the column).
+template <bool ENTRY, bool BIN>
+__device__ __forceinline__ LaneValue load_value(int32_t type, uint32_t width, const void* values, const uint8_t* binary,
+                                                bool valid, uint64_t idx, uint64_t n_values) {
   LaneValue v;
   v.key = 0;
+  v.lo = 0;
   v.rel = v.len = 0;
   v.slow = nullptr;
-  if (type == PQG_BYTE_ARRAY) {
+  const bool fixed = BIN && (type == PQG_INT96 || type == PQG_FIXED_LEN_BYTE_ARRAY);
+  if (type == PQG_BYTE_ARRAY || fixed) {
     // the value's bytes are [a0, a1) (addresses), as its two offsets say
     uint64_t a0 = 0, a1 = 0;
-    if (valid) {
+    if (fixed) {
+      binary = (const uint8_t*)values;
+      if (valid) {
+        a0 = (uint64_t)(uintptr_t)values + idx * (uint64_t)width;
+        a1 = a0 + width;
+      }
+    } else if (valid) {
       int64_t a = ((const int64_t*)values)[idx], b = ((const int64_t*)values)[idx + 1];
       if (ENTRY) {
         int64_t lo = ((const int64_t*)values)[0], hi = ((const int64_t*)values)[n_values];
@@ -218,7 +346,8 @@ __device__ __forceinline__ LaneValue load_value(int32_t type, const void* values
     // value that reaches into the cut tail, lies outside the buffer or more than 4 GiB into it is read
     // with plain byte loads inside its own bytes
     uint64_t first = vm ? rdl64(a0, (uint32_t)__builtin_ctzll(vm)) & ~3ull : 0;
-    if (first < (uint64_t)(uintptr_t)binary) first = (uint64_t)(uintptr_t)binary;
+    if (first < (uint64_t)(uintptr_t)binary)  // fixed: the first whole dword inside the column (a value before it: byte loads)
+      first = fixed ? ((uint64_t)(uintptr_t)binary + 3u) & ~3ull : (uint64_t)(uintptr_t)binary;
     const uint64_t last = vm ? rdl64(a1, 63u - (uint32_t)__builtin_clzll(vm)) : 0;
     const uint64_t whole = last > first ? (last - first) & ~3ull : 0;
     v.rs = make_rsrc((const uint8_t*)(uintptr_t)first, whole);
@@ -246,9 +375,9 @@ __device__ __forceinline__ void stage_image(uint8_t* lds, const uint8_t* __restr
 // ---- k_filter_dict ---------------------------------------------------------------------------
 // Grid (64-entry words / FT_WPB, table leaves): a wave evaluates its leaf on 64 entries of the leaf's
 // dictionary, lane = entry, and stores the ballot as one word of the leaf's table. Entries past n_entries: 0.
-__global__ __launch_bounds__(64 * FT_WPB) void k_filter_dict(const uint8_t* __restrict__ image, uint32_t image_bytes,
-                                                             const FilterDictTab* __restrict__ dt,
-                                                             uint64_t* __restrict__ tables) {
+template <bool BIN>
+__device__ __forceinline__ void filter_dict_words(const uint8_t* __restrict__ image, uint32_t image_bytes,
+                                                  const FilterDictTab* __restrict__ dt, uint64_t* __restrict__ tables) {
   extern __shared__ __align__(16) uint8_t lds[];
   stage_image(lds, image, image_bytes);
   __syncthreads();
@@ -265,10 +394,20 @@ __global__ __launch_bounds__(64 * FT_WPB) void k_filter_dict(const uint8_t* __re
   const uint32_t type = uni(nd.type);
   const uint64_t e = word * 64 + lane_id();
   const bool valid = e < n;
-  LaneValue v = load_value<true>((int32_t)type, ds.values, ds.binary, valid, e, n);
-  if (type != PQG_BYTE_ARRAY) v.key = filter_key((int)type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, (uint64_t)v.key);
-  const uint64_t m = __ballot(valid && leaf_eval(nd, valid, v, cells, lbytes));
+  const LaneValue v = leaf_value<BIN>(
+      nd, (int32_t)type, valid, load_value<true, BIN>((int32_t)type, BIN ? uni(nd.width) : 0u, ds.values, ds.binary, valid, e, n));
+  const uint64_t m = __ballot(valid && leaf_eval<BIN>(nd, valid, v, cells, lbytes));
   if (lane_id() == 0) gst(&tables[uni64(dt->leaf_off[ni]) + word], m);
+}
+__global__ __launch_bounds__(64 * FT_WPB) void k_filter_dict(const uint8_t* __restrict__ image, uint32_t image_bytes,
+                                                             const FilterDictTab* __restrict__ dt,
+                                                             uint64_t* __restrict__ tables) {
+  filter_dict_words<false>(image, image_bytes, dt, tables);
+}
+__global__ __launch_bounds__(64 * FT_WPB) void k_filter_dict_bin(const uint8_t* __restrict__ image, uint32_t image_bytes,
+                                                                 const FilterDictTab* __restrict__ dt,
+                                                                 uint64_t* __restrict__ tables) {
+  filter_dict_words<true>(image, image_bytes, dt, tables);
 }
 
 // ---- k_filter_eval ---------------------------------------------------------------------------
@@ -280,7 +419,7 @@ __global__ __launch_bounds__(64 * FT_WPB) void k_filter_dict(const uint8_t* __re
 // FilterRecDev, a repeated slot and every leaf under a CONTAINS node are skipped, and a CONTAINS node's 64
 // records of step s are word tile * 64 + s of its leaf's record bitmap (k_filter_contains wrote it): lane i
 // loads the word of node i one step ahead.
-template <bool DICT, bool REC>
+template <bool DICT, bool REC, bool BIN>
 __device__ __forceinline__ void filter_eval_tile(const uint8_t* __restrict__ image, uint32_t image_bytes,
                                                  const FilterCols& cols, uint64_t n_rows, uint64_t n_tiles,
                                                  const uint64_t* __restrict__ rank, uint64_t* __restrict__ bitmap,
@@ -393,7 +532,8 @@ __device__ __forceinline__ void filter_eval_tile(const uint8_t* __restrict__ ima
         }
         continue;
       }
-      const LaneValue v = load_value<false>(type, c.values, c.binary, valid, idx, 0);
+      const uint32_t width = BIN && li < n_leaves ? uni(nodes[uni(order[li])].width) : 0u;  // the column's, in its leaves
+      const LaneValue v = load_value<false, BIN>(type, width, c.values, c.binary, valid, idx, 0);
       // every leaf on this column (the column is loaded once per step)
       while (li < n_leaves) {
         const uint32_t ni = uni(order[li]);
@@ -403,9 +543,8 @@ __device__ __forceinline__ void filter_eval_tile(const uint8_t* __restrict__ ima
           li++;
           continue;
         }
-        LaneValue lv = v;
-        if (type != PQG_BYTE_ARRAY) lv.key = filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, (uint64_t)v.key);
-        const uint64_t m = __ballot(leaf_eval(nd, valid, lv, cells, lbytes));
+        const LaneValue lv = leaf_value<BIN>(nd, type, valid, v);
+        const uint64_t m = __ballot(leaf_eval<BIN>(nd, valid, lv, cells, lbytes));
         if (lane == ni) node_mask = m;
         li++;
       }
@@ -434,7 +573,17 @@ __global__ __launch_bounds__(64 * FT_WPB) void k_filter_eval(const uint8_t* __re
                                                              const FilterDictTab* __restrict__ dt,
                                                              const uint64_t* __restrict__ tables,
                                                              uint64_t* __restrict__ dict_bad) {
-  filter_eval_tile<DICT, false>(image, image_bytes, cols, n_rows, n_tiles, rank, bitmap, sel, dt, tables, dict_bad);
+  filter_eval_tile<DICT, false, false>(image, image_bytes, cols, n_rows, n_tiles, rank, bitmap, sel, dt, tables, dict_bad);
+}
+template <bool DICT>
+__global__ __launch_bounds__(64 * FT_WPB) void k_filter_eval_bin(const uint8_t* __restrict__ image, uint32_t image_bytes,
+                                                                 const FilterCols cols, uint64_t n_rows, uint64_t n_tiles,
+                                                                 const uint64_t* __restrict__ rank,
+                                                                 uint64_t* __restrict__ bitmap, uint64_t* __restrict__ sel,
+                                                                 const FilterDictTab* __restrict__ dt,
+                                                                 const uint64_t* __restrict__ tables,
+                                                                 uint64_t* __restrict__ dict_bad) {
+  filter_eval_tile<DICT, false, true>(image, image_bytes, cols, n_rows, n_tiles, rank, bitmap, sel, dt, tables, dict_bad);
 }
 // pqg_filter_run_records with contains leaves: the records form, a kernel of its own
 __global__ __launch_bounds__(64 * FT_WPB) void k_filter_eval_records(const uint8_t* __restrict__ image, uint32_t image_bytes,
@@ -444,7 +593,13 @@ __global__ __launch_bounds__(64 * FT_WPB) void k_filter_eval_records(const uint8
                                                                      const FilterRecDev* __restrict__ rd,
                                                                      const uint64_t* __restrict__ tables,
                                                                      uint64_t* __restrict__ dict_bad) {
-  filter_eval_tile<true, true>(image, image_bytes, cols, n_rows, n_tiles, rank, bitmap, sel, &rd->dt, tables, dict_bad);
+  filter_eval_tile<true, true, false>(image, image_bytes, cols, n_rows, n_tiles, rank, bitmap, sel, &rd->dt, tables, dict_bad);
+}
+__global__ __launch_bounds__(64 * FT_WPB) void k_filter_eval_records_bin(
+    const uint8_t* __restrict__ image, uint32_t image_bytes, const FilterCols cols, uint64_t n_rows, uint64_t n_tiles,
+    const uint64_t* __restrict__ rank, uint64_t* __restrict__ bitmap, uint64_t* __restrict__ sel,
+    const FilterRecDev* __restrict__ rd, const uint64_t* __restrict__ tables, uint64_t* __restrict__ dict_bad) {
+  filter_eval_tile<true, true, true>(image, image_bytes, cols, n_rows, n_tiles, rank, bitmap, sel, &rd->dt, tables, dict_bad);
 }
 
 // ---- k_filter_emit ---------------------------------------------------------------------------
@@ -472,7 +627,7 @@ __global__ __launch_bounds__(64 * FT_WPB) void k_filter_emit(const uint64_t* __r
 // ---- launch ----------------------------------------------------------------------------------
 hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_bytes, const FilterCols& cols,
                          uint64_t n_rows, uint64_t* scratch, uint64_t* bitmap, int64_t* row_ids, uint64_t row_ids_capacity,
-                         pqg_filter_result* result, const FilterDictTab* d_dict, const FilterDictTab* h_dict) {
+                         pqg_filter_result* result, const FilterDictTab* d_dict, const FilterDictTab* h_dict, bool bin) {
   const uint64_t n_tiles = filter_tiles(n_rows);
   uint64_t* rank = scratch;
   uint64_t* sel = rank + (uint64_t)cols.n_nullable * n_tiles;
@@ -484,8 +639,9 @@ hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_
   if (d_dict) {
     if (hipMemsetAsync(dict_bad, 0, 8 * PQG_FILTER_MAX_NODES, st) != hipSuccess) return hipGetLastError();
     if (h_dict->n_tables)
-      hipLaunchKernelGGL(k_filter_dict, dim3((uint32_t)((h_dict->max_words + FT_WPB - 1) / FT_WPB), h_dict->n_tables),
-                         dim3(64 * FT_WPB), image_bytes, st, d_image, image_bytes, d_dict, tables);
+      hipLaunchKernelGGL(bin ? k_filter_dict_bin : k_filter_dict,
+                         dim3((uint32_t)((h_dict->max_words + FT_WPB - 1) / FT_WPB), h_dict->n_tables), dim3(64 * FT_WPB),
+                         image_bytes, st, d_image, image_bytes, d_dict, tables);
   }
   if (cols.n_nullable) {
     if (n_tiles)
@@ -495,7 +651,7 @@ hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_
   }
   if (!d_dict) {
     if (n_tiles)
-      hipLaunchKernelGGL(k_filter_eval<false>, dim3(wgs), dim3(64 * FT_WPB), image_bytes, st, d_image, image_bytes, cols,
+      hipLaunchKernelGGL(bin ? k_filter_eval_bin<false> : k_filter_eval<false>, dim3(wgs), dim3(64 * FT_WPB), image_bytes, st, d_image, image_bytes, cols,
                          n_rows, n_tiles, rank, bitmap, sel, (const FilterDictTab*)nullptr, (const uint64_t*)nullptr,
                          (uint64_t*)nullptr);
     hipLaunchKernelGGL(k_filter_scan<true>, dim3(1), dim3(256), 0, st, sel, n_tiles, cols, totals, bad, result,
@@ -503,7 +659,7 @@ hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_
   } else {
     const uint32_t lds_bytes = image_bytes + (h_dict->in_lds ? (uint32_t)h_dict->table_words * 8u : 0u);
     if (n_tiles)
-      hipLaunchKernelGGL(k_filter_eval<true>, dim3(wgs), dim3(64 * FT_WPB), lds_bytes, st, d_image, image_bytes, cols,
+      hipLaunchKernelGGL(bin ? k_filter_eval_bin<true> : k_filter_eval<true>, dim3(wgs), dim3(64 * FT_WPB), lds_bytes, st, d_image, image_bytes, cols,
                          n_rows, n_tiles, rank, bitmap, sel, d_dict, tables, dict_bad);
     hipLaunchKernelGGL((k_filter_scan<true, true>), dim3(1), dim3(256), 0, st, sel, n_tiles, cols, totals, bad, result,
                        dict_bad);
@@ -625,14 +781,12 @@ __global__ __launch_bounds__(256) void k_filter_rec_scan(const FilterCols cols, 
 // record may span tiles): 64-bit agent-scope atomic OR without return, only when non-zero. The bitmaps were
 // zeroed before the launch. Nothing is written for a record index of -1 or >= n_rows (such a slot never
 // hits), so every store stays inside ceil(n_rows / 64) words.
-template <uint32_t K>
-__global__ __launch_bounds__(64 * FT_WPB) void k_filter_contains(const uint8_t* __restrict__ image, uint32_t image_bytes,
-                                                                 const FilterCols cols, uint64_t n_rows, uint64_t s_tiles,
-                                                                 const FilterRecDev* __restrict__ rd,
-                                                                 const uint64_t* __restrict__ starts,
-                                                                 const uint64_t* __restrict__ vals,
-                                                                 const uint64_t* __restrict__ tables,
-                                                                 uint64_t* __restrict__ dict_bad) {
+template <uint32_t K, bool BIN>
+__device__ __forceinline__ void filter_contains_tile(const uint8_t* __restrict__ image, uint32_t image_bytes,
+                                                     const FilterCols& cols, uint64_t n_rows, uint64_t s_tiles,
+                                                     const FilterRecDev* __restrict__ rd, const uint64_t* __restrict__ starts,
+                                                     const uint64_t* __restrict__ vals, const uint64_t* __restrict__ tables,
+                                                     uint64_t* __restrict__ dict_bad) {
   static_assert(K <= FILTER_CONTAINS_GROUP, "a group holds at most FILTER_CONTAINS_GROUP leaves");
   extern __shared__ __align__(16) uint8_t lds[];
   stage_image(lds, image, image_bytes);
@@ -713,15 +867,14 @@ __global__ __launch_bounds__(64 * FT_WPB) void k_filter_contains(const uint8_t* 
         hit[k] = __ballot(((w >> (id & 63u)) & 1u) != 0);
       }
     } else {
-      const LaneValue v = load_value<false>(type, c.values, c.binary, valid, idx, 0);
+      const LaneValue v = load_value<false, BIN>(type, BIN ? uni(nodes[ni[0]].width) : 0u, c.values, c.binary, valid, idx, 0);
 #pragma unroll
       for (uint32_t k = 0; k < K; k++) {
         hit[k] = 0;
         if (k >= cnt) continue;
         const FilterDevNode nd = nodes[ni[k]];
-        LaneValue lv = v;
-        if (type != PQG_BYTE_ARRAY) lv.key = filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, (uint64_t)v.key);
-        hit[k] = __ballot(valid && leaf_eval(nd, valid, lv, cells, lbytes));
+        const LaneValue lv = leaf_value<BIN>(nd, type, valid, v);
+        hit[k] = __ballot(valid && leaf_eval<BIN>(nd, valid, lv, cells, lbytes));
       }
     }
     uint64_t any = 0;
@@ -773,6 +926,27 @@ __global__ __launch_bounds__(64 * FT_WPB) void k_filter_contains(const uint8_t* 
   }
 }
 
+template <uint32_t K>
+__global__ __launch_bounds__(64 * FT_WPB) void k_filter_contains(const uint8_t* __restrict__ image, uint32_t image_bytes,
+                                                                 const FilterCols cols, uint64_t n_rows, uint64_t s_tiles,
+                                                                 const FilterRecDev* __restrict__ rd,
+                                                                 const uint64_t* __restrict__ starts,
+                                                                 const uint64_t* __restrict__ vals,
+                                                                 const uint64_t* __restrict__ tables,
+                                                                 uint64_t* __restrict__ dict_bad) {
+  filter_contains_tile<K, false>(image, image_bytes, cols, n_rows, s_tiles, rd, starts, vals, tables, dict_bad);
+}
+template <uint32_t K>
+__global__ __launch_bounds__(64 * FT_WPB) void k_filter_contains_bin(const uint8_t* __restrict__ image, uint32_t image_bytes,
+                                                                     const FilterCols cols, uint64_t n_rows, uint64_t s_tiles,
+                                                                     const FilterRecDev* __restrict__ rd,
+                                                                     const uint64_t* __restrict__ starts,
+                                                                     const uint64_t* __restrict__ vals,
+                                                                     const uint64_t* __restrict__ tables,
+                                                                     uint64_t* __restrict__ dict_bad) {
+  filter_contains_tile<K, true>(image, image_bytes, cols, n_rows, s_tiles, rd, starts, vals, tables, dict_bad);
+}
+
 // ---- launch ----------------------------------------------------------------------------------
 // d_rec / h_rec: the FilterRecDev on the device and on the host (h_rec->rt.bitmaps already points into the
 // scratch: filter_records_bitmaps).
@@ -782,7 +956,7 @@ uint64_t* filter_records_bitmaps(uint64_t* scratch, uint64_t n_rows, uint32_t n_
 hipError_t launch_filter_records(hipStream_t st, const uint8_t* d_image, uint32_t image_bytes, const FilterCols& cols,
                                  uint64_t n_rows, uint64_t* scratch, uint64_t* bitmap, int64_t* row_ids,
                                  uint64_t row_ids_capacity, pqg_filter_result* result, const FilterRecDev* d_rec,
-                                 const FilterRecDev* h_rec) {
+                                 const FilterRecDev* h_rec, bool bin) {
   const FilterDictTab& hd = h_rec->dt;
   const FilterRecTab& hr = h_rec->rt;
   const uint64_t n_tiles = filter_tiles(n_rows), s_tiles = filter_tiles(hr.max_slots);
@@ -800,7 +974,7 @@ hipError_t launch_filter_records(hipStream_t st, const uint8_t* d_image, uint32_
   if (hipMemsetAsync(R.flags, 0, 8 * (PQG_FILTER_MAX_NODES + (size_t)hr.n_leaves * hr.bitmap_words), st) != hipSuccess)
     return hipGetLastError();
   if (hd.n_tables)
-    hipLaunchKernelGGL(k_filter_dict, dim3((uint32_t)((hd.max_words + FT_WPB - 1) / FT_WPB), hd.n_tables),
+    hipLaunchKernelGGL(bin ? k_filter_dict_bin : k_filter_dict, dim3((uint32_t)((hd.max_words + FT_WPB - 1) / FT_WPB), hd.n_tables),
                        dim3(64 * FT_WPB), image_bytes, st, d_image, image_bytes, d_dict, tables);
   if (hr.n_rep) {
     if (s_tiles)
@@ -812,6 +986,9 @@ hipError_t launch_filter_records(hipStream_t st, const uint8_t* d_image, uint32_
       uint32_t largest = 1;
       for (uint32_t g = 0; g < hr.n_groups; g++) largest = hr.group_n[g] > largest ? hr.group_n[g] : largest;
       auto* kernel = largest == 1 ? k_filter_contains<1> : largest == 2 ? k_filter_contains<2> : k_filter_contains<FILTER_CONTAINS_GROUP>;
+      if (bin)
+        kernel = largest == 1 ? k_filter_contains_bin<1>
+                              : largest == 2 ? k_filter_contains_bin<2> : k_filter_contains_bin<FILTER_CONTAINS_GROUP>;
       hipLaunchKernelGGL(kernel, dim3(s_wgs, hr.n_groups), dim3(64 * FT_WPB), lds_bytes, st, d_image, image_bytes, cols, n_rows,
                          s_tiles, d_rec, R.starts, R.vals, tables, dict_bad);
     }
@@ -823,7 +1000,7 @@ hipError_t launch_filter_records(hipStream_t st, const uint8_t* d_image, uint32_
                        result, (const uint64_t*)nullptr);
   }
   if (n_tiles)
-    hipLaunchKernelGGL(k_filter_eval_records, dim3(wgs), dim3(64 * FT_WPB), lds_bytes, st, d_image, image_bytes, cols,
+    hipLaunchKernelGGL(bin ? k_filter_eval_records_bin : k_filter_eval_records, dim3(wgs), dim3(64 * FT_WPB), lds_bytes, st, d_image, image_bytes, cols,
                        n_rows, n_tiles, rank, bitmap, sel, d_rec, tables, dict_bad);
   // the verdicts of the repeated columns stand behind those of the flat nullable ones
   FilterCols all = cols;

@@ -3,7 +3,8 @@
 // and the device image, and the binding of a run's columns and dictionaries to the program's slots
 // (pqg::filter_bind, pqg::filter_bind_records).
 // Plain C++ with no HIP in it, so that it also builds alone under the sanitizers
-// (tests/c/filter_sanitize.cpp, tests/c/filter_dict_sanitize.cpp, tests/c/filter_records_sanitize.cpp).
+// (tests/c/filter_sanitize.cpp, tests/c/filter_dict_sanitize.cpp, tests/c/filter_records_sanitize.cpp,
+// tests/c/filter_typed_sanitize.cpp).
 #include <stdio.h>
 #include <string.h>
 
@@ -51,6 +52,35 @@ int compare_bytes(const uint8_t* a, uint32_t na, const uint8_t* b, uint32_t nb) 
   const int c = n ? memcmp(a, b, n) : 0;
   if (c) return c < 0 ? -1 : 1;
   return na < nb ? -1 : (na > nb ? 1 : 0);
+}
+
+// BINARY_AS_SIGNED_INTEGER_COMPARATOR (PrimitiveComparator.java:214-279): the signs (of the first byte; an
+// empty value is non-negative), the longer side's extra leading bytes against the shorter side's sign
+// padding, then the common tail as unsigned bytes.
+int compare_signed(const uint8_t* a, uint32_t na, const uint8_t* b, uint32_t nb) {
+  const bool neg_a = na > 0 && (a[0] & 0x80u), neg_b = nb > 0 && (b[0] & 0x80u);
+  if (neg_a != neg_b) return neg_a ? -1 : 1;
+  const int pad = neg_a ? 0xFF : 0;
+  if (na < nb) {
+    for (uint32_t i = 0; i < nb - na; i++)
+      if (b[i] != pad) return b[i] > pad ? -1 : 1;
+    b += nb - na;
+  } else if (na > nb) {
+    for (uint32_t i = 0; i < na - nb; i++)
+      if (a[i] != pad) return a[i] > pad ? 1 : -1;
+    a += na - nb;
+  }
+  const uint32_t n = na < nb ? na : nb;
+  const int c = n ? memcmp(a, b, n) : 0;
+  return c < 0 ? -1 : (c > 0 ? 1 : 0);
+}
+
+bool is_binary(int type) { return type == PQG_BYTE_ARRAY || type == PQG_INT96 || type == PQG_FIXED_LEN_BYTE_ARRAY; }
+
+// Float16 key of a literal cell (two little-endian bytes; the length was checked)
+int64_t float16_key(const uint8_t* lb, uint64_t cell) {
+  const uint8_t* p = lb + (uint32_t)cell;
+  return pqg::filter_key_float16((uint32_t)p[0] | ((uint32_t)p[1] << 8));
 }
 
 std::atomic<uint64_t> g_serial{1};
@@ -109,17 +139,12 @@ int contains_rewrite(const std::vector<pqg_filter_node>& p, int i, int* code, in
   return col[0];
 }
 
-}  // namespace
-
-extern "C" {
-
-int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* column_types, int n_cols,
-                      const uint64_t* literals, int n_literals, const uint8_t* literal_bytes,
-                      uint64_t n_literal_bytes, pqg_filter** out, pqg_status* st) {
-  if (!out) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: out is null");
-  *out = nullptr;
+// pqg_filter_create (`bare`: the columns came as plain physical types, INT96 / FLBA are refused) and
+// pqg_filter_create_typed: one validation path.
+int create_filter(const pqg_filter_node* nodes, int n_nodes, const pqg_filter_column_type* columns, int n_cols, bool bare,
+                  const uint64_t* literals, int n_literals, const uint8_t* literal_bytes, uint64_t n_literal_bytes,
+                  pqg_filter** out, pqg_status* st) {
   if (!nodes || n_nodes <= 0) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no nodes");
-  if (n_cols < 0 || (n_cols > 0 && !column_types)) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no column types");
   if (n_literals < 0 || (n_literals > 0 && !literals)) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no literal table");
   if (n_literal_bytes > 0 && !literal_bytes) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no literal bytes");
   if (n_nodes > kMaxInputNodes) return fail(st, PQG_ERR_UNSUPPORTED, -1, "filter: more than 4096 nodes");
@@ -152,10 +177,25 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
     }
     if (nd.left != -1 || nd.right != -1) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: a leaf has children");
     if (nd.column < 0 || nd.column >= n_cols) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: column out of range");
-    const int type = column_types[nd.column];
+    const pqg_filter_column_type& ct = columns[nd.column];
+    const int type = ct.physical_type;
     if (type < PQG_BOOLEAN || type > PQG_FIXED_LEN_BYTE_ARRAY) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown column type");
-    if (type == PQG_INT96 || type == PQG_FIXED_LEN_BYTE_ARRAY)
+    if (bare && (type == PQG_INT96 || type == PQG_FIXED_LEN_BYTE_ARRAY))
       return fail(st, PQG_ERR_UNSUPPORTED, i, "filter: INT96 / FIXED_LEN_BYTE_ARRAY columns are not supported");
+    const int order = ct.binary_order;
+    if (order < PQG_FILTER_ORDER_UNSIGNED_BYTES || order > PQG_FILTER_ORDER_FLOAT16)
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unknown binary order");
+    if (!is_binary(type) && (ct.type_length || order))
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: type_length or binary_order on a column that is not binary");
+    if (type == PQG_BYTE_ARRAY && ct.type_length) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: type_length on a BYTE_ARRAY column");
+    if (type == PQG_FIXED_LEN_BYTE_ARRAY && ct.type_length < 1)
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: FIXED_LEN_BYTE_ARRAY column without a type_length");
+    if (type == PQG_INT96 && ct.type_length != 0 && ct.type_length != 12)
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: INT96 column with a type_length other than 12");
+    if (type == PQG_INT96 && order != PQG_FILTER_ORDER_SIGNED_INTEGER)
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: INT96 compares as a signed integer only");
+    if (order == PQG_FILTER_ORDER_FLOAT16 && (type != PQG_FIXED_LEN_BYTE_ARRAY || ct.type_length != 2))
+      return fail(st, PQG_ERR_INVALID_ARG, i, "filter: FLOAT16 order on a column that is not FIXED_LEN_BYTE_ARRAY(2)");
     if ((nd.flags & PQG_FILTER_UNSIGNED) && type != PQG_INT32 && type != PQG_INT64)
       return fail(st, PQG_ERR_INVALID_ARG, i, "filter: unsigned order on a column that is not INT32 / INT64");
     if ((uint64_t)nd.literal_begin + nd.n_literals > (uint64_t)n_literals)
@@ -167,11 +207,13 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
     if (ineq && null_lit) return fail(st, PQG_ERR_INVALID_ARG, i, "filter: lt / ltEq / gt / gtEq against null");
     if (set ? (nd.n_literals == 0 && !null_lit) : nd.n_literals != (null_lit ? 0u : 1u))
       return fail(st, PQG_ERR_INVALID_ARG, i, "filter: wrong number of literals");
-    if (type == PQG_BYTE_ARRAY)
+    if (is_binary(type))
       for (uint32_t k = 0; k < nd.n_literals; k++) {
         const uint64_t cell = literals[nd.literal_begin + k];
         if ((cell & 0xFFFFFFFFull) + (cell >> 32) > n_literal_bytes)
           return fail(st, PQG_ERR_INVALID_ARG, i, "filter: BYTE_ARRAY literal past the literal bytes");
+        if (order == PQG_FILTER_ORDER_FLOAT16 && (cell >> 32) != 2)
+          return fail(st, PQG_ERR_INVALID_ARG, i, "filter: FLOAT16 literal that is not 2 bytes long");
       }
   }
   for (int i = 0; i < n_nodes; i++)
@@ -198,7 +240,8 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
   pqg_filter* f = new (std::nothrow) pqg_filter();
   if (!f) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: out of memory");
   f->serial = g_serial.fetch_add(1);
-  f->column_types.assign(column_types, column_types + n_cols);
+  f->columns.assign(columns, columns + n_cols);
+  for (int c = 0; c < n_cols; c++) f->column_types.push_back(columns[c].physical_type);
   if (n_literal_bytes) f->bytes.assign(literal_bytes, literal_bytes + n_literal_bytes);
   std::vector<int> orig;  // program node -> input node
   for (int i = 0; i < n_nodes; i++) {
@@ -251,10 +294,18 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
   for (pqg_filter_node& nd : f->program) {
     if (!is_leaf(nd.op)) continue;
     const int type = f->column_types[(size_t)nd.column];
+    const int order = f->columns[(size_t)nd.column].binary_order;
+    if (order || type == PQG_INT96 || type == PQG_FIXED_LEN_BYTE_ARRAY) f->binary_paths = true;
     if (nd.n_literals > pqg::FILTER_IN_LINEAR) {
       uint64_t* b = f->cells.data() + nd.literal_begin;
       const bool uns = (nd.flags & PQG_FILTER_UNSIGNED) != 0;
-      if (type == PQG_BYTE_ARRAY)
+      if (order == PQG_FILTER_ORDER_SIGNED_INTEGER)
+        std::sort(b, b + nd.n_literals, [lb](uint64_t x, uint64_t y) {
+          return compare_signed(lb + (uint32_t)x, (uint32_t)(x >> 32), lb + (uint32_t)y, (uint32_t)(y >> 32)) < 0;
+        });
+      else if (order == PQG_FILTER_ORDER_FLOAT16)
+        std::sort(b, b + nd.n_literals, [lb](uint64_t x, uint64_t y) { return float16_key(lb, x) < float16_key(lb, y); });
+      else if (is_binary(type))
         std::sort(b, b + nd.n_literals, [lb](uint64_t x, uint64_t y) {
           return compare_bytes(lb + (uint32_t)x, (uint32_t)(x >> 32), lb + (uint32_t)y, (uint32_t)(y >> 32)) < 0;
         });
@@ -266,10 +317,52 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
     if (std::find(f->slot_column.begin(), f->slot_column.end(), nd.column) == f->slot_column.end())
       f->slot_column.push_back(nd.column);
   }
+  // the image's cells, leaf by leaf: one per literal, or three under FILTER_DEV_KEY128 (every literal of the
+  // leaf fits 16 bytes once its redundant sign bytes are gone, and so does every value it can meet below the
+  // byte-wise path) while cells and bytes together stay inside what the limits give an image
+  std::vector<uint64_t> img_cells;
+  std::vector<uint32_t> img_begin(f->program.size(), 0);
+  std::vector<uint8_t> dev_flags(f->program.size(), 0);
+  size_t spare = (8u * PQG_FILTER_MAX_LITERALS + PQG_FILTER_MAX_LITERAL_BYTES - 8u * f->cells.size() - f->bytes.size()) / 16u;
+  for (size_t i = 0; i < f->program.size(); i++) {
+    const pqg_filter_node& nd = f->program[i];
+    if (!is_leaf(nd.op)) continue;
+    const pqg_filter_column_type& ct = f->columns[(size_t)nd.column];
+    const int type = ct.physical_type;
+    const uint64_t* raw = f->cells.data() + nd.literal_begin;
+    img_begin[i] = (uint32_t)img_cells.size();
+    if (ct.binary_order == PQG_FILTER_ORDER_FLOAT16) {
+      dev_flags[i] = pqg::FILTER_DEV_FLOAT16;
+      for (uint32_t k = 0; k < nd.n_literals; k++) img_cells.push_back((uint64_t)float16_key(lb, raw[k]));
+    } else if (ct.binary_order == PQG_FILTER_ORDER_SIGNED_INTEGER) {
+      dev_flags[i] = pqg::FILTER_DEV_SIGNED;
+      const uint32_t width = type == PQG_INT96 ? 12u : (uint32_t)ct.type_length;
+      bool keys = nd.n_literals <= spare && (type == PQG_BYTE_ARRAY || width <= pqg::FILTER_KEY128_BYTES);
+      int64_t hi;
+      uint64_t lo;
+      for (uint32_t k = 0; keys && k < nd.n_literals; k++)
+        keys = pqg::filter_key128(lb + (uint32_t)raw[k], (uint32_t)(raw[k] >> 32), &hi, &lo);
+      if (keys) {
+        dev_flags[i] |= pqg::FILTER_DEV_KEY128;
+        spare -= nd.n_literals;
+      }
+      for (uint32_t k = 0; k < nd.n_literals; k++) {
+        img_cells.push_back(raw[k]);
+        if (!keys) continue;
+        (void)pqg::filter_key128(lb + (uint32_t)raw[k], (uint32_t)(raw[k] >> 32), &hi, &lo);
+        img_cells.push_back((uint64_t)hi);
+        img_cells.push_back(lo);
+      }
+    } else {
+      for (uint32_t k = 0; k < nd.n_literals; k++)
+        img_cells.push_back(is_binary(type) ? raw[k]
+                                            : (uint64_t)pqg::filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, raw[k]));
+    }
+  }
   pqg::FilterDevHeader h{};
   h.n_nodes = (uint32_t)f->program.size();
   h.n_slots = (uint32_t)f->slot_column.size();
-  h.n_cells = (uint32_t)f->cells.size();
+  h.n_cells = (uint32_t)img_cells.size();
   h.n_bytes = (uint32_t)f->bytes.size();
   h.cells_off = (uint32_t)(sizeof(h) + h.n_nodes * sizeof(pqg::FilterDevNode) + PQG_FILTER_MAX_NODES);
   h.bytes_off = h.cells_off + 8u * h.n_cells;
@@ -289,31 +382,53 @@ int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* 
     const pqg_filter_node& nd = f->program[i];
     pqg::FilterDevNode d{};
     d.op = (uint8_t)nd.op;
-    d.flags = (uint8_t)(nd.flags | (contained[i] ? pqg::FILTER_DEV_CONTAINED : 0u));
+    d.flags = (uint8_t)(nd.flags | dev_flags[i] | (contained[i] ? pqg::FILTER_DEV_CONTAINED : 0u));
     if (is_leaf(nd.op)) {
-      const int type = f->column_types[(size_t)nd.column];
-      d.type = (uint8_t)type;
+      const pqg_filter_column_type& ct = f->columns[(size_t)nd.column];
+      d.type = (uint8_t)ct.physical_type;
       d.slot = (uint8_t)(std::find(f->slot_column.begin(), f->slot_column.end(), nd.column) - f->slot_column.begin());
       d.n_lit = (uint16_t)nd.n_literals;
-      d.lit_begin = nd.literal_begin;
-      for (uint32_t k = 0; k < nd.n_literals; k++) {
-        const uint64_t raw = f->cells[nd.literal_begin + k];
-        const uint64_t cell = type == PQG_BYTE_ARRAY
-                                  ? raw
-                                  : (uint64_t)pqg::filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, raw);
-        memcpy(img + h.cells_off + 8u * (nd.literal_begin + k), &cell, 8);
-      }
+      d.lit_begin = img_begin[i];
+      d.width = ct.physical_type == PQG_INT96 ? 12u : ct.physical_type == PQG_FIXED_LEN_BYTE_ARRAY ? (uint32_t)ct.type_length : 0u;
     } else {
       d.left = (uint8_t)nd.left;
       d.right = (uint8_t)(nd.right < 0 ? 0 : nd.right);
     }
     memcpy(img + sizeof(h) + i * sizeof(d), &d, sizeof(d));
   }
+  if (h.n_cells) memcpy(img + h.cells_off, img_cells.data(), 8u * h.n_cells);
   if (h.n_bytes) memcpy(img + h.bytes_off, lb, h.n_bytes);
   memcpy(img, &h, sizeof(h));
   *out = f;
   if (st) fail(st, PQG_OK, -1, "");
   return PQG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pqg_filter_create(const pqg_filter_node* nodes, int n_nodes, const int32_t* column_types, int n_cols,
+                      const uint64_t* literals, int n_literals, const uint8_t* literal_bytes,
+                      uint64_t n_literal_bytes, pqg_filter** out, pqg_status* st) {
+  if (!out) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: out is null");
+  *out = nullptr;
+  if (n_cols < 0 || (n_cols > 0 && !column_types)) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no column types");
+  std::vector<pqg_filter_column_type> columns((size_t)n_cols);
+  for (int c = 0; c < n_cols; c++) columns[(size_t)c] = pqg_filter_column_type{column_types[c], 0, 0, 0};
+  return create_filter(nodes, n_nodes, columns.data(), n_cols, true, literals, n_literals, literal_bytes, n_literal_bytes,
+                       out, st);
+}
+
+int pqg_filter_create_typed(const pqg_filter_node* nodes, int n_nodes, const pqg_filter_column_type* columns, int n_cols,
+                            const uint64_t* literals, int n_literals, const uint8_t* literal_bytes,
+                            uint64_t n_literal_bytes, pqg_filter** out, pqg_status* st) {
+  if (!out) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: out is null");
+  *out = nullptr;
+  if (n_cols < 0 || (n_cols > 0 && !columns)) return fail(st, PQG_ERR_INVALID_ARG, -1, "filter: no column types");
+  for (int c = 0; c < n_cols; c++)
+    if (columns[c].reserved) return fail(st, PQG_ERR_INVALID_ARG, c, "filter: reserved field of a column type is not 0");
+  return create_filter(nodes, n_nodes, columns, n_cols, false, literals, n_literals, literal_bytes, n_literal_bytes, out, st);
 }
 
 int pqg_filter_program(const pqg_filter* filter, pqg_filter_node* out, int cap) {

@@ -158,11 +158,11 @@ inline uint64_t filter_tiles(uint64_t n_rows) { return (n_rows + PQG_FILTER_TILE
 inline uint64_t filter_scratch_words(uint64_t n_rows, uint32_t n_nullable, uint64_t dict_words = 0) {
   return ((uint64_t)n_nullable + 1) * filter_tiles(n_rows) + 2 * PQG_FILTER_MAX_NODES + dict_words;
 }
-// d_dict: the FilterDictTab on the device (null: no dictionary columns), h_dict: the same on the host
+// d_dict: the FilterDictTab on the device (null: no dictionary columns), h_dict: the same on the host;
+// bin: the program has a binary-order or fixed-width-binary leaf (pqg_filter::binary_paths): the *_bin kernels
 hipError_t launch_filter(hipStream_t st, const uint8_t* d_image, uint32_t image_bytes, const FilterCols& cols,
                          uint64_t n_rows, uint64_t* scratch, uint64_t* bitmap, int64_t* row_ids, uint64_t row_ids_capacity,
-                         pqg_filter_result* result, const FilterDictTab* d_dict = nullptr,
-                         const FilterDictTab* h_dict = nullptr);
+                         pqg_filter_result* result, const FilterDictTab* d_dict, const FilterDictTab* h_dict, bool bin);
 // pqgpu_filter.hip: pqg_filter_run_records with contains leaves (FilterRecDev: pqgpu_filter.h). The scratch is
 // launch_filter's with dictionaries, then flags[PQG_FILTER_MAX_NODES], bitmaps[n_leaves][tiles(n_rows) * 64],
 // starts[n_rep][tiles(max_slots)], vals[n_rep][tiles(max_slots)] (dict_words = PQG_FILTER_MAX_NODES + table_words).
@@ -174,7 +174,7 @@ uint64_t* filter_records_bitmaps(uint64_t* scratch, uint64_t n_rows, uint32_t n_
 hipError_t launch_filter_records(hipStream_t st, const uint8_t* d_image, uint32_t image_bytes, const FilterCols& cols,
                                  uint64_t n_rows, uint64_t* scratch, uint64_t* bitmap, int64_t* row_ids,
                                  uint64_t row_ids_capacity, pqg_filter_result* result, const FilterRecDev* d_rec,
-                                 const FilterRecDev* h_rec);
+                                 const FilterRecDev* h_rec, bool bin);
 // pqgpu_take.hip: pqg_take. scratch (u64 words): keep[n_tiles], rank[n_cols][n_tiles], kept[n_cols][n_tiles],
 // bytes[n_cols][n_tiles] (per-tile counts, scanned in place), totals[1 + 3 n_cols]
 struct TakeColDev;

@@ -258,6 +258,20 @@ class FilterResult(C.Structure):
 
 assert C.sizeof(FilterNode) == 32 and C.sizeof(FilterColumn) == 40 and C.sizeof(FilterResult) == 16
 
+# binary comparators (pqg_filter_binary_order, pqg_filter_create_typed)
+FILTER_ORDER_UNSIGNED_BYTES, FILTER_ORDER_SIGNED_INTEGER, FILTER_ORDER_FLOAT16 = range(3)
+FILTER_ORDER_NAMES = {"unsigned_bytes": FILTER_ORDER_UNSIGNED_BYTES, "signed_integer": FILTER_ORDER_SIGNED_INTEGER,
+                      "float16": FILTER_ORDER_FLOAT16}
+
+
+class FilterColumnType(C.Structure):
+    """pqg_filter_column_type (16 bytes): a column's physical type, element width and binary comparator."""
+    _fields_ = [("physical_type", C.c_int32), ("type_length", C.c_int32), ("binary_order", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+assert C.sizeof(FilterColumnType) == 16
+
 # record filter on dictionary ids (pqg_filter_run_dict)
 FILTER_DICT_LDS_BYTES = 8192  # PQG_FILTER_DICT_LDS_BYTES: verdict tables up to this many bytes are staged in LDS
 

@@ -335,6 +335,8 @@ class Decoder:
         for i, cd in enumerate(batch.columns):
             n = batch.column_slots[i]
             w = abi.elem_width(cd["physical_type"], cd["type_length"])
+            if int(cd.get("flags", 0)) & abi.COLUMN_DICTIONARY_IDS:
+                w = max(w, 4)  # uint32 ids, whatever the type's width (a FIXED_LEN_BYTE_ARRAY may be narrower)
             binary = None
             if cd["physical_type"] == abi.BYTE_ARRAY:
                 n_off = n + 1  # offsets[n + 1]

@@ -8,6 +8,9 @@ A small predicate DSL named after parquet-mr's FilterApi (filter2/predicate/Filt
     sel.count, sel.bitmap, sel.row_ids
 
 `contains(leaf)` is FilterApi.contains on a repeated column: Decoder.filter_records evaluates it per record.
+`col(i, order=...)` names the comparator of a binary column ("unsigned_bytes", "signed_integer" for DECIMAL and
+INT96, "float16") and makes FIXED_LEN_BYTE_ARRAY and INT96 columns filterable (pqg_filter_create_typed); their
+literals are bytes, e.g. `decimal_bytes(-129)`.
 `None` is the null literal (eq / not_eq, or a member of an in_ / not_in set). `compile` flattens a
 predicate to the node, literal and byte tables of the C ABI; `Filter` is the created pqg_filter
 (validated and rewritten without not(), as FilterCompat.get does with LogicalInverseRewriter).
@@ -25,11 +28,15 @@ OP_NAMES.update({abi.FILTER_AND: "and", abi.FILTER_OR: "or", abi.FILTER_NOT: "no
 
 
 class Column:
-    """A column of the row group by index; unsigned=True for UINT_32 / UINT_64 annotated columns."""
+    """A column of the row group by index; unsigned=True for UINT_32 / UINT_64 annotated columns; order: the
+    comparator of a BYTE_ARRAY / FIXED_LEN_BYTE_ARRAY / INT96 column (None: as pqg_filter_create has it)."""
 
-    def __init__(self, index, unsigned=False):
+    def __init__(self, index, unsigned=False, order=None):
+        if order is not None and order not in abi.FILTER_ORDER_NAMES:
+            raise ValueError(f"order must be None or one of {sorted(abi.FILTER_ORDER_NAMES)}, not {order!r}")
         self.index = int(index)
         self.unsigned = bool(unsigned)
+        self.order = order
 
 
 class Predicate:
@@ -48,8 +55,20 @@ class Predicate:
         return f"{OP_NAMES[self.op]}(col{self.column.index}{'u' if self.column.unsigned else ''}, {vals!r})"
 
 
-def col(index, unsigned=False):
-    return Column(index, unsigned)
+def col(index, unsigned=False, order=None):
+    return Column(index, unsigned, order)
+
+
+def decimal_bytes(unscaled, length=None):
+    """The big-endian two's-complement bytes of the integer `unscaled` (a DECIMAL's unscaled value, an INT96):
+    the fewest that hold it, or sign-extended to `length` bytes. For literals of a "signed_integer" column."""
+    unscaled = int(unscaled)
+    n = (unscaled if unscaled >= 0 else ~unscaled).bit_length() // 8 + 1
+    if length is not None:
+        if length < n:
+            raise OverflowError(f"{unscaled} does not fit {length} bytes")
+        n = int(length)
+    return unscaled.to_bytes(n, "big", signed=True)
 
 
 def _leaf(op, column, values):
@@ -95,11 +114,12 @@ def literal_cell(physical_type, value):
 class Compiled:
     """The C ABI tables of a predicate: nodes (post-order, root last), literal cells, literal bytes."""
 
-    def __init__(self, nodes, literals, literal_bytes, column_types):
+    def __init__(self, nodes, literals, literal_bytes, column_types, typed=None):
         self.nodes = nodes                  # list of (op, column, left, right, flags, literal_begin, n_literals)
         self.literals = literals            # list of int cells
         self.literal_bytes = literal_bytes  # bytes
         self.column_types = column_types    # list of pqg_physical_type
+        self.typed = typed                  # None, or list of (physical_type, type_length, binary_order): create_typed
 
 
 def column_types(columns):
@@ -118,10 +138,19 @@ def column_types(columns):
     return out
 
 
+def _type_length(column):
+    """type_length of a column object (of its dictionary for an ids column); 0 for a bare type."""
+    if getattr(column, "flags", 0) & abi.COLUMN_DICTIONARY_IDS:
+        column = getattr(column, "dictionary", None)
+    return int(getattr(column, "type_length", 0) or 0)
+
+
 def compile(pred, columns):
-    """Flatten `pred` (post-order: left, right, node) to the tables pqg_filter_create takes."""
+    """Flatten `pred` (post-order: left, right, node) to the tables pqg_filter_create takes, or, when a column
+    the predicate names carries an `order`, pqg_filter_create_typed (Compiled.typed)."""
     types = column_types(columns)
     nodes, literals, blob = [], [], bytearray()
+    orders = {}  # column index -> order name, of the columns named with one
 
     def walk(p):
         if p.children:
@@ -135,9 +164,13 @@ def compile(pred, columns):
             flags |= abi.FILTER_NULL_LITERAL
             values = [v for v in values if v is not None]
         t = types[c.index] if 0 <= c.index < len(types) else None
+        order = getattr(c, "order", None)
+        if order is not None:
+            if orders.setdefault(c.index, order) != order:
+                raise ValueError(f"column {c.index} is named with two orders: {orders[c.index]!r} and {order!r}")
         begin = len(literals)
         for v in values:
-            if t == abi.BYTE_ARRAY:
+            if t == abi.BYTE_ARRAY or (order is not None and t in (abi.INT96, abi.FIXED_LEN_BYTE_ARRAY)):
                 b = bytes(v)
                 literals.append(len(blob) | (len(b) << 32))
                 blob.extend(b)
@@ -149,23 +182,52 @@ def compile(pred, columns):
         return len(nodes) - 1
 
     walk(pred)
-    return Compiled(nodes, literals, bytes(blob), types)
+    typed = None
+    if orders:
+        typed = []
+        for i, t in enumerate(types):
+            tl = _type_length(columns[i]) if t == abi.FIXED_LEN_BYTE_ARRAY else 0
+            typed.append((t, tl, abi.FILTER_ORDER_NAMES[orders[i]] if i in orders else 0))
+    return Compiled(nodes, literals, bytes(blob), types, typed)
 
 
-def create(nodes, literals, literal_bytes, types, n_literals=None, n_literal_bytes=None):
-    """pqg_filter_create over raw tables -> (rc, handle, status). The table sizes may be overridden
-    (tests hand in sizes that disagree with the tables)."""
+def _tables(nodes, literals, literal_bytes):
+    """The node, literal and byte tables as ctypes / numpy arrays (never empty: one spare element each)."""
     arr = (abi.FilterNode * max(1, len(nodes)))()
     for i, nd in enumerate(nodes):
         (arr[i].op, arr[i].column, arr[i].left, arr[i].right, arr[i].flags, arr[i].literal_begin,
          arr[i].n_literals) = nd
     lit = np.asarray(literals, dtype=np.uint64) if len(literals) else np.zeros(1, dtype=np.uint64)
     blob = np.frombuffer(bytes(literal_bytes) + b"\0", dtype=np.uint8)
+    return arr, lit, blob
+
+
+def create(nodes, literals, literal_bytes, types, n_literals=None, n_literal_bytes=None):
+    """pqg_filter_create over raw tables -> (rc, handle, status). The table sizes may be overridden
+    (tests hand in sizes that disagree with the tables)."""
+    arr, lit, blob = _tables(nodes, literals, literal_bytes)
     ty = np.asarray(list(types) or [0], dtype=np.int32)
     h = C.c_void_p()
     st = abi.Status()
     rc = native.lib().pqg_filter_create(
         C.addressof(arr), len(nodes), ty.ctypes.data, len(types), lit.ctypes.data,
+        len(literals) if n_literals is None else n_literals, blob.ctypes.data,
+        len(literal_bytes) if n_literal_bytes is None else n_literal_bytes, C.byref(h), C.byref(st))
+    return rc, h, st
+
+
+def create_typed(nodes, literals, literal_bytes, columns, n_literals=None, n_literal_bytes=None):
+    """pqg_filter_create_typed over raw tables -> (rc, handle, status); `columns`: (physical_type, type_length,
+    binary_order) or (..., reserved) per column."""
+    arr, lit, blob = _tables(nodes, literals, literal_bytes)
+    ct = (abi.FilterColumnType * max(1, len(columns)))()
+    for i, c in enumerate(columns):
+        ct[i].physical_type, ct[i].type_length, ct[i].binary_order = c[:3]
+        ct[i].reserved = c[3] if len(c) > 3 else 0
+    h = C.c_void_p()
+    st = abi.Status()
+    rc = native.lib().pqg_filter_create_typed(
+        C.addressof(arr), len(nodes), C.addressof(ct), len(columns), lit.ctypes.data,
         len(literals) if n_literals is None else n_literals, blob.ctypes.data,
         len(literal_bytes) if n_literal_bytes is None else n_literal_bytes, C.byref(h), C.byref(st))
     return rc, h, st
@@ -177,8 +239,11 @@ class Filter:
     def __init__(self, pred, columns):
         self.compiled = compile(pred, columns)
         c = self.compiled
-        rc, self.handle, st = create(c.nodes, c.literals, c.literal_bytes, c.column_types)
-        native.check(rc, st, "pqg_filter_create")
+        if c.typed is not None:
+            rc, self.handle, st = create_typed(c.nodes, c.literals, c.literal_bytes, c.typed)
+        else:
+            rc, self.handle, st = create(c.nodes, c.literals, c.literal_bytes, c.column_types)
+        native.check(rc, st, "pqg_filter_create_typed" if c.typed is not None else "pqg_filter_create")
         self.n_cols = len(c.column_types)
 
     def program(self):

@@ -36,6 +36,8 @@ EXPORTS = [
     "pqg_filter_run_dict", "pqg_decode_dictionary",
     # ... on list columns: contains()
     "pqg_filter_run_records",
+    # binary comparators: DECIMAL, FIXED_LEN_BYTE_ARRAY, INT96, FLOAT16
+    "pqg_filter_create_typed",
     # row selection (the rows a bitmap keeps, as compact columns)
     "pqg_take",
     # ... with repeated columns: whole records
@@ -109,6 +111,7 @@ def lib():
         L.pqg_frame_chunk.argtypes = [vp, u64, C.c_int64, i32, vp, i32, C.POINTER(i32), C.POINTER(abi.Status)]
         L.pqg_pages_from_headers.argtypes = [vp, i32, i32, u64, i32, vp, vp, i32, C.POINTER(i32), C.POINTER(abi.Status)]
         L.pqg_filter_create.argtypes = [vp, i32, vp, i32, vp, i32, vp, u64, C.POINTER(vp), C.POINTER(abi.Status)]
+        L.pqg_filter_create_typed.argtypes = [vp, i32, vp, i32, vp, i32, vp, u64, C.POINTER(vp), C.POINTER(abi.Status)]
         L.pqg_filter_program.argtypes = [vp, vp, i32]
         L.pqg_filter_destroy.argtypes = [vp]
         L.pqg_filter_run.argtypes = [vp, vp, vp, i32, u64, vp, vp, u64, vp]
