@@ -445,7 +445,14 @@ static int delta_init(jdelta* r, jstream* s) {
   int32_t mb_size = (int32_t)mini;
   if (mb_num < 0 || mb_size <= 0) return PQG_ERR_CORRUPT;
   if ((e = read_uvarint(s, &total))) return e;
-  if (total < 0) return PQG_ERR_CORRUPT;
+  /* allocateValuesBuffer :83-87: (int) Math.ceil((double) total / mbSize) miniblocks. A count of at most
+   * -mbSize gives a negative array size; one in (-mbSize, 0) rounds to no miniblock: the buffer holds the
+   * first value alone, no block is loaded (valuesBuffered 1 is not < total) and every read finds
+   * valuesRead >= totalValueCount, as with a count of 0 */
+  if (total < 0) {
+    if ((int64_t)total <= -(int64_t)mb_size) return PQG_ERR_CORRUPT;
+    total = 0;
+  }
   int64_t mb_count = ((int64_t)total + mb_size - 1) / mb_size;   /* Math.ceil :84 */
   int64_t cap = mb_count * mb_size + 1;
   r->buf = (int64_t*)calloc((size_t)cap, sizeof(int64_t));

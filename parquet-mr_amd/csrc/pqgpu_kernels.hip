@@ -2877,7 +2877,9 @@ __device__ __forceinline__ void delta_expand(const DSeg& S, uint32_t nb, uint32_
   const uint32_t j0 = lane * E;
   const bool lane_in = j0 < block;
   const uint32_t m = lane_in ? j0 / mbs : 0u;
-  const uint32_t jm = j0 - m * mbs;
+  // (a lane past the block, when the block is shorter than 64 * E, reads as delta 0 of miniblock 0: its
+  // own index would address up to 64 * E * 8 bytes from the block's data, past the staged bytes)
+  const uint32_t jm = lane_in ? j0 - m * mbs : 0u;
   const uint32_t mb_bytes = mbs / 8u;  // bytes per bit of width
   // wide stores need the run's first value E*W-aligned (runs start at multiples of E from `out`)
   constexpr uint32_t RUN = E * (uint32_t)sizeof(T);
@@ -3000,7 +3002,8 @@ __device__ __forceinline__ void delta_expand_seg(const DSeg& S, uint32_t nb, uin
     const uint32_t g = g0 + lane;
     const bool lane_in = g < n_seg;
     const uint32_t bb = lane_in ? g / SB : 0u;
-    const uint32_t j0 = (g - bb * SB) * L;  // the segment's first delta in its block
+    // (a lane past the batch's segments reads as segment 0 of block 0, staged, and stores nothing)
+    const uint32_t j0 = lane_in ? (g - bb * SB) * L : 0u;  // the segment's first delta in its block
     const uint32_t m = j0 / mbs, jm = j0 - m * mbs;
     const uint32_t data = (uint32_t)__shfl((int)b_data, (int)bb), wpos = (uint32_t)__shfl((int)b_wpos, (int)bb);
     const uint32_t nmb = (uint32_t)__shfl((int)b_nmb, (int)bb);
@@ -3008,8 +3011,13 @@ __device__ __forceinline__ void delta_expand_seg(const DSeg& S, uint32_t nb, uin
     // the block's miniblock widths (<= 8 bytes at wpos), the lane's width and data offset
     const uint32_t wa = wpos & ~3u, sb = wpos & 3u;
     const uint32_t y0 = S.w32(wa), y1 = S.w32(wa + 4), y2 = S.w32(wa + 8);
-    const uint32_t wlo = __builtin_amdgcn_alignbyte(y1, y0, sb), whi = __builtin_amdgcn_alignbyte(y2, y1, sb);
-    const uint32_t wl = m < nmb ? ((m < 4u ? wlo >> (8u * m) : whi >> (8u * (m - 4u))) & 0xFFu) : 0u;
+    // only the nmb used width bytes count: the reader never looks at the width of an unread miniblock of a
+    // last block (any byte value), so such a lane gets width 0 and the position after the used miniblocks'
+    // data, inside the staged bytes (the walk staged dbytes + 12), not a sum over arbitrary bytes
+    const uint32_t uml = nmb >= 4u ? 0xFFFFFFFFu : (1u << (8u * nmb)) - 1u;
+    const uint32_t umh = nmb <= 4u ? 0u : (nmb >= 8u ? 0xFFFFFFFFu : (1u << (8u * (nmb - 4u))) - 1u);
+    const uint32_t wlo = __builtin_amdgcn_alignbyte(y1, y0, sb) & uml, whi = __builtin_amdgcn_alignbyte(y2, y1, sb) & umh;
+    const uint32_t wl = (m < 4u ? wlo >> (8u * m) : whi >> (8u * (m - 4u))) & 0xFFu;
     const uint32_t blo = m >= 4u ? wlo : (m ? wlo & ((1u << (8u * m)) - 1u) : 0u);
     const uint32_t bhi = m <= 4u ? 0u : whi & ((1u << (8u * (m - 4u))) - 1u);
     const uint32_t dbase = data + (__builtin_amdgcn_sad_u8(blo, 0u, 0u) + __builtin_amdgcn_sad_u8(bhi, 0u, 0u)) * mb_bytes;
@@ -3385,16 +3393,24 @@ __device__ int delta_stream(DSeg& S, uint32_t p, uint32_t end, uint32_t want, ty
   const uint32_t mbn = (uint32_t)seg_uvar<true>(S, p, end - p, len);
   if ((uint64_t)p + len > end) return PQG_ERR_EOF;
   p += len;
-  // DeltaBinaryPackingConfig ctor :34-41 (double division, % 8)
-  if (mbn == 0 || (int32_t)mbn < 0 || (int32_t)block < 0) return mbn == 0 ? PQG_ERR_DELTA_CONFIG : PQG_ERR_CORRUPT;
-  if ((block % mbn) != 0 || ((block / mbn) % 8u) != 0) return PQG_ERR_DELTA_CONFIG;
+  // DeltaBinaryPackingConfig ctor :34-41: (double) block / mbn % 8 == 0 on Java ints, i.e. block is a
+  // multiple of 8 * mbn whatever the signs (the quotient of two ints is never rounded to an integer);
+  // the precondition comes first, a negative count of miniblocks or block size is refused after it
+  if (mbn == 0) return PQG_ERR_DELTA_CONFIG;
+  if ((int64_t)(int32_t)block % (8 * (int64_t)(int32_t)mbn) != 0) return PQG_ERR_DELTA_CONFIG;
+  if ((int32_t)mbn < 0 || (int32_t)block < 0) return PQG_ERR_CORRUPT;
   const uint32_t mbs = block / mbn;
   if (mbs == 0) return PQG_ERR_CORRUPT;
   if (p >= end) return PQG_ERR_EOF;
-  const uint32_t total = (uint32_t)seg_uvar<true>(S, p, end - p, len);
+  uint32_t total = (uint32_t)seg_uvar<true>(S, p, end - p, len);
   if ((uint64_t)p + len > end) return PQG_ERR_EOF;
   p += len;
-  if ((int32_t)total < 0) return PQG_ERR_CORRUPT;
+  // allocateValuesBuffer :83-87 takes ceil(count / mbs) miniblocks: a count of at most -mbs is a negative
+  // array size, one in (-mbs, 0) rounds to no miniblock and the page reads as an empty one
+  if ((int32_t)total < 0) {
+    if ((int64_t)(int32_t)total <= -(int64_t)mbs) return PQG_ERR_CORRUPT;
+    total = 0;
+  }
   if (p >= end) return PQG_ERR_EOF;
   const uint64_t fraw = seg_uvar<false>(S, p, end - p, len);
   if ((uint64_t)p + len > end) return PQG_ERR_EOF;

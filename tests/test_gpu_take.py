@@ -388,8 +388,10 @@ def test_host_refusals(decoder, main):
     L = native.lib()
     dev = decoder.device
     buf = torch.zeros(4096, dtype=torch.uint8, device=dev)
-    state = torch.zeros(64, dtype=torch.uint8, device=dev)
-    p, counts, result = buf.data_ptr(), state.data_ptr() + 16, state.data_ptr()
+    # one pqg_take_result, then a pqg_take_counts per column of the largest call below
+    state = torch.zeros(C.sizeof(abi.TakeResult) + abi.TAKE_MAX_COLUMNS * C.sizeof(abi.TakeCounts), dtype=torch.uint8,
+                        device=dev)
+    p, counts, result = buf.data_ptr(), state.data_ptr() + C.sizeof(abi.TakeResult), state.data_ptr()
 
     def column(**kw):
         c = abi.TakeColumn(physical_type=abi.INT64, max_def=1, values=p, def_levels=p + 1024, n_values=10, out_values=p + 2048,
