@@ -53,6 +53,13 @@ __device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l);
 }
 
+// v_writelane_b32: `old` with lane l (uniform) replaced by the uniform x. This clang has no
+// __builtin_amdgcn_writelane; the asm label binds the declaration to the LLVM intrinsic.
+extern "C" __device__ int pqg_writelane_i32(int x, int l, int old) __asm("llvm.amdgcn.writelane.i32");
+__device__ __forceinline__ uint32_t wrl(uint32_t x, uint32_t l, uint32_t old) {
+  return (uint32_t)pqg_writelane_i32((int)x, (int)l, (int)old);
+}
+
 __device__ __forceinline__ uint32_t uni(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }

@@ -165,6 +165,83 @@ __device__ __forceinline__ void predecode(PreWin& pw, uint32_t B, int w) {
   pw.flg = flg;
 }
 
+// readUnsignedVarInt of a header of at most 4 bytes whose first dword is d: the header length
+// (4 when no byte of d ends the varint: the caller treats that as slow) and the 7-bit groups
+// compacted, branch-free.
+__device__ __forceinline__ uint32_t varint4(uint32_t d, uint32_t& hl) {
+  const uint32_t stop = ~d & 0x80808080u;  // stop bit of each of 4 bytes
+  hl = ((uint32_t)__builtin_ctz(stop | 0x80000000u) >> 3) + 1u;
+  const uint32_t dm = d & (0xFFFFFFFFu >> (32u - 8u * hl));
+  return (dm & 0x7Fu) | ((dm >> 1) & 0x3F80u) | ((dm >> 2) & 0x1FC000u) | ((dm >> 3) & 0xFE00000u);
+}
+
+// Successor-only pre-decode of the window [B, B + 256) for the dictionary list walk: what the
+// chain needs of a position is where the next header would be, nothing else. Lane l, byte b of
+// js: window offset of the successor of position B + 4 l + b, 0 when the chain stops there (the
+// successor leaves the window, the position is past the section end, or the header is one for the
+// scalar path: a varint of 5 bytes or more, 0 groups, a header or RLE value crossing the section
+// end). Bit b of slowm / inm: scalar-path header / position inside the section. Branch-free;
+// counts and values are parsed later, only at the positions the chain visited (walk_header).
+template <bool LDS_ONLY>
+__device__ __forceinline__ void predecode_succ(PreWin& pw, uint32_t B, int w, uint32_t sec_end, uint32_t& js,
+                                               uint32_t& slowm, uint32_t& inm) {
+  pw.B = B;
+  const uint32_t base = B + 4u * lane_id();
+  if (!LDS_ONLY && !seg_has(pw, B, 264u)) seg_fill(pw, B & ~15u);
+  const uint32_t d0 = seg32(pw, base), d1 = seg32(pw, base + 4);
+  const uint32_t nb = ((uint32_t)w + 7u) >> 3;
+  js = slowm = inm = 0;
+#pragma unroll
+  for (uint32_t b = 0; b < 4; b++) {
+    const uint32_t p = base + b;
+    const uint32_t d = b ? __builtin_amdgcn_alignbyte(d1, d0, b) : d0;  // bytes p .. p + 3
+    uint32_t hl;
+    const uint32_t v = varint4(d, hl);
+    const uint32_t pk = d & 1u;
+    const uint32_t groups = v >> 1;
+    // 256 groups or more leave the window at any w > 0 (and add nothing at w = 0)
+    const uint32_t adv = pk ? __umul24(groups < 256u ? groups : 256u, (uint32_t)w) : nb;
+    const uint32_t nx = p + hl + adv;
+    // (bitwise on 0 / 1 words: && and || would come out as exec-masked branches)
+    const uint32_t in = p < sec_end;
+    const uint32_t slow = in & ((uint32_t)((~d & 0x80808080u) == 0u) | (pk & (uint32_t)(groups == 0u)) |
+                                (uint32_t)(p + hl > sec_end) | ((pk ^ 1u) & (uint32_t)(nx > sec_end)));
+    const uint32_t nn = nx < sec_end ? nx : (pk ? sec_end : nx);  // packed: readFully of what is left
+    const uint32_t j = (in & (slow ^ 1u) & (uint32_t)(nn - B < 256u)) ? nn - B : 0u;
+    js |= j << (8u * b);
+    slowm |= slow << b;
+    inm |= in << b;
+  }
+}
+
+// The header at window offset o of the pre-decoded window (a fast one: at most 4 bytes, inside
+// the section), parsed by the lane that owns it in the batch: count (RLE 0 = "to the page end" is
+// left to the caller), record payload (raw RLE value clamped to 2^31 - 1, or 0x80000000 | packed
+// data start) and the next header position. Reads [B + o, B + o + 8) of the staged segment.
+__device__ __forceinline__ void walk_header(const PreWin& pw, uint32_t o, int w, uint32_t sec_end, bool& pk,
+                                            uint32_t& c, uint32_t& payload, uint32_t& nx) {
+  const uint32_t p = pw.B + o, a = p & ~3u;
+  const uint32_t d0 = seg32(pw, a), d1 = seg32(pw, a + 4), d2 = seg32(pw, a + 8);
+  const uint32_t x0 = __builtin_amdgcn_alignbyte(d1, d0, p & 3u), x1 = __builtin_amdgcn_alignbyte(d2, d1, p & 3u);
+  uint32_t hl;
+  const uint32_t v = varint4(x0, hl);
+  const uint32_t nb = ((uint32_t)w + 7u) >> 3;
+  pk = x0 & 1u;
+  if (pk) {  // (header >>> 1) groups of 8 values, groups * w bytes
+    const uint32_t groups = v >> 1;  // < 2^27
+    c = groups * 8u;
+    payload = 0x80000000u | (p + hl);
+    const uint64_t e = (uint64_t)p + hl + (uint64_t)groups * (uint32_t)w;
+    nx = e < sec_end ? (uint32_t)e : sec_end;  // readFully of what is left
+  } else {   // count, then ceil(w/8) little-endian bytes, not masked
+    const uint32_t y = (uint32_t)((((uint64_t)x1 << 32) | x0) >> (8u * hl));
+    const uint32_t vv = nb == 4 ? y : y & ((1u << (8u * nb)) - 1u);
+    c = v >> 1;
+    payload = vv > 0x7FFFFFFFu ? 0x7FFFFFFFu : vv;
+    nx = p + hl + nb;
+  }
+}
+
 // Scalar re-decode of one header at `pos` (rare: varints longer than 5 bytes,
 // 0 or >= 2^28 groups). Bytes come through uniform buffer loads.
 __device__ __forceinline__ uint32_t sbyte(rsrc_t rs, uint32_t p) {
@@ -267,11 +344,9 @@ __device__ __forceinline__ typename DictVal<W>::T load_dict(rsrc_t d, uint32_t i
 
 constexpr uint32_t DICT_LDS_BYTES = 8192;   // dictionary staged in LDS per workgroup when it fits
 
-// Per-wave LDS of k_dict.
+// Per-wave LDS of the dictionary walk.
 struct DictWaveLds {
   uint8_t seg[SEG_BYTES];  // page bytes [seg_lo, seg_lo + SEG_BYTES)
-  uint64_t ent[256];       // window position k: next header position | (count | packed << 31) << 32
-  uint32_t val[256];       // window position k: RLE raw value, or packed data start
 };
 
 // ---------------------------------------------------------------------------
@@ -344,16 +419,17 @@ __device__ __forceinline__ uint32_t wave_incl_scan_sat(uint32_t x, uint32_t cap)
   return x;
 }
 
-// List walk: the same windows and pre-decode as dict_walk_pj, with the window's chain and its
-// records built without per-position masks.
+// List walk: 256-byte windows whose chain and records are built without per-position masks.
 //   chain    the successors of a lane's 4 positions are packed into one dword (byte b: window
 //            offset of the successor of position 4 * lane + b, 0 = the chain stops there — a
-//            successor is always past its header, so 0 is free); each step is one v_readlane, a
-//            byte extract and one lane select that appends the position to a list VGPR (lane t =
-//            t-th header of the batch): one loop branch per run, no per-position mark words.
-//   records  lane t reads its header's count / payload from an LDS table (one 8-byte entry per
-//            window position), a saturating DPP scan gives the first values, and lane t stores
-//            record k + t: one store per run instead of a ballot compaction over 256 positions.
+//            successor is always past its header, so 0 is free), built by predecode_succ, which
+//            parses nothing else; each step is one v_readlane, a byte extract and one v_writelane
+//            that appends the position to a list VGPR (lane t = t-th header of the batch): one
+//            loop branch per run, no per-position mark words.
+//   records  lane t parses the header it holds from the staged bytes (walk_header: count and
+//            payload, only at the positions the chain visited), a saturating DPP scan gives the
+//            first values, and lane t stores record k + t: one store per run instead of a ballot
+//            compaction over 256 positions.
 // A window with more than 64 headers on its chain is taken in several batches.
 // Semantics are those of dict_walk_pj (readNext :80-109, the scalar slow path for long varints,
 // 0 / huge group counts and headers crossing the section end).
@@ -362,9 +438,6 @@ __device__ __forceinline__ void dict_walk_ls(DictWaveLds& L, PreWin& win, uint32
                                              uint32_t sec_end, int w, uint64_t* rec, uint32_t* chunk_run,
                                              uint32_t CH, uint32_t sh, int page, uint64_t* err, ErrCount err_count,
                                              uint32_t& n_rec, uint32_t& n_ok) {
-  typedef uint64_t __attribute__((may_alias)) u64a;
-  typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-  typedef u64x2 __attribute__((may_alias)) u64x2a;
   const uint32_t lane = lane_id();
   uint32_t pos = sec_beg + 1;  // RunLengthBitPackingHybridDecoder stream position
   uint32_t produced = 0, k = 0;
@@ -423,44 +496,24 @@ __device__ __forceinline__ void dict_walk_ls(DictWaveLds& L, PreWin& win, uint32
 #ifdef PQG_DIAG
     dg_win++;
 #endif
-    predecode<SMALL, (bool)0>(win, B, w);
-    uint32_t js = 0, nn[4], slowm = 0, inm = 0;
-    uint64_t ent[4];
-#pragma unroll
-    for (uint32_t b = 0; b < 4; b++) {
-      const uint32_t p = B + 4u * lane + b;
-      const uint32_t f = (win.flg >> (8u * b)) & 0xFFu;
-      const uint32_t hl = f >> 2;
-      const uint32_t nx = win.nxt[b];
-      const bool in = p < sec_end;
-      const bool slow = in && ((f & 2u) || p + hl > sec_end || (!(f & 1u) && nx > sec_end));
-      nn[b] = (f & 1u) ? (nx < sec_end ? nx : sec_end) : nx;  // packed: readFully of what is left
-      const uint32_t j = (!in || slow || nn[b] - B >= 256u) ? 0u : nn[b] - B;
-      js |= j << (8u * b);
-      slowm |= (slow ? 1u : 0u) << b;
-      inm |= (in ? 1u : 0u) << b;
-      ent[b] = (uint64_t)win.val[b] | ((uint64_t)(win.cnt[b] | ((f & 1u) << 31)) << 32);
-    }
-    wave_sync();  // the previous window's table reads are done
-    ((u64x2a*)L.ent)[2u * lane] = u64x2{ent[0], ent[1]};
-    ((u64x2a*)L.ent)[2u * lane + 1u] = u64x2{ent[2], ent[3]};
-    wave_sync();
+    uint32_t js, slowm, inm;
+    predecode_succ<SMALL>(win, B, w, sec_end, js, slowm, inm);
     DIAG_ADD(dg_pre, dg_t0);
-    uint32_t q = pos - B, nq = 0;
+    uint32_t q = uni(pos - B), nq = 0, t = 0, nxh = 0;
     while (true) {  // batches of at most 64 chain positions
-      uint32_t t = 0, lst = 0;
+      uint32_t lst = 0;
+      t = 0;
       DIAG_T(dg_t1);
 #ifdef PQG_DIAG
       dg_bat++;
 #endif
-      while (true) {
-        q = uni(q);
-        lst = lane == t ? q : lst;  // v_cmp + v_cndmask
+      do {  // one step per run: append q to the list (lane t), read its successor
+        lst = wrl(q, t, lst);
         nq = (rdl(js, q >> 2) >> ((q & 3u) << 3)) & 0xFFu;
         t++;
-        if (nq == 0u || t == (uint32_t)WAVE) break;
-        q = nq;
-      }
+        if (nq == 0u) break;
+        q = nq;  // (a full batch leaves with q == nq: the next batch's first position)
+      } while (t < (uint32_t)WAVE);
       t = uni(t);
       nq = uni(nq);
       DIAG_ADD(dg_chain, dg_t1);
@@ -471,16 +524,13 @@ __device__ __forceinline__ void dict_walk_ls(DictWaveLds& L, PreWin& win, uint32
       const bool last_run = nq != 0u || (!((rdl(slowm, ql) >> qb) & 1u) && ((rdl(inm, ql) >> qb) & 1u));
       const uint32_t n_v = last_run ? t : t - 1u;
       const uint32_t cap = N - produced;
-      uint32_t c = 0, payload = 0;
-      if (lane < n_v) {
-        const uint64_t e = ((const u64a*)L.ent)[lst];
-        const uint32_t cw = (uint32_t)(e >> 32), vv = (uint32_t)e;
-        const bool pk = cw >> 31;
-        c = cw & 0x7FFFFFFFu;
-        if (!pk && c == 0) c = cap;  // Java: currentCount goes negative, the value repeats forever
-        c = c < cap ? c : cap;
-        payload = pk ? (0x80000000u | vv) : (vv > 0x7FFFFFFFu ? 0x7FFFFFFFu : vv);
-      }
+      // lane t < n_v parses the header it holds (the other lanes parse window offset 0 for nothing)
+      bool pk;
+      uint32_t c, payload;
+      walk_header(win, lst, w, sec_end, pk, c, payload, nxh);
+      if (!pk && c == 0) c = cap;  // Java: currentCount goes negative, the value repeats forever
+      c = c < cap ? c : cap;
+      if (lane >= n_v) c = 0;
       const uint32_t inc = wave_incl_scan_sat(c, cap);
       uint32_t st = __shfl_up(inc, 1);
       if (lane == 0) st = 0;
@@ -509,7 +559,7 @@ __device__ __forceinline__ void dict_walk_ls(DictWaveLds& L, PreWin& win, uint32
     if (!q_in) {
       pos = B + q;  // at or past the section end: RLE_PAST_END on the next iteration
     } else if (!q_slow) {
-      pos = pick4(nn, qb, ql);  // leaves the window
+      pos = rdl(nxh, t - 1u);  // leaves the window: the last list lane parsed this header
     } else {
       // scalar re-decode of the header at q (readNext :80-109)
       pos = B + q;
@@ -540,8 +590,8 @@ __device__ __forceinline__ void dict_walk_ls(DictWaveLds& L, PreWin& win, uint32
 // One wave per page (4 per workgroup): the run records of RLE_DICTIONARY / PLAIN_DICTIONARY
 // pages (DictionaryValuesReader.initFromPage :48-64 + RunLengthBitPackingHybridDecoder.readNext
 // :80-109). The page section is staged in LDS; a 256-byte window is pre-decoded in parallel
-// (every lane parses a run header at each of its 4 byte positions) into LDS tables, and the
-// serial chain is one ds_read_b64 + ds_read_b32 per run.
+// (every lane finds the successor of a header at each of its 4 byte positions), the serial chain
+// is one v_readlane per run, and the chain's headers are parsed one per lane (dict_walk_ls).
 // One wave per page (4 per workgroup; `group` is the workgroup's index among the walkers).
 template <int W>
 __device__ __forceinline__ void dict_runs_body(const uint8_t* __restrict__ bytes, uint64_t n_bytes,
