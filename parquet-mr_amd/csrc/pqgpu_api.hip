@@ -1411,7 +1411,7 @@ int pqg_assemble(pqg_ctx* ctx, const uint8_t* d_def_levels, const uint8_t* d_rep
   const uint8_t* rl = r > 0 ? d_rep_levels : nullptr;
   // the single pass: status words, totals and the ticket zeroed, then one kernel (outputs + totals)
   auto emit = [&]() -> hipError_t {
-    hipError_t e2 = hipMemsetAsync(ctx->asm_scratch.p, 0, cnt_bytes + sizeof(uint64_t) * pqg::ASM_MAX_DEPTHS + 16, s);
+    hipError_t e2 = hipMemsetAsync(ctx->asm_scratch.p, 0, cnt_bytes + sizeof(uint64_t) * pqg::ASM_TOTAL_WORDS, s);
     if (e2 == hipSuccess) e2 = pqg::launch_assemble(s, dl, rl, n_slots, P, counts, n_blocks, totals, ticket, 1);
     if (e2 == hipSuccess && n_blocks == 0)  // no slots: closing offsets only (offsets[0] = 0)
       for (int k = 0; k < depth && e2 == hipSuccess; k++)
@@ -1421,13 +1421,14 @@ int pqg_assemble(pqg_ctx* ctx, const uint8_t* d_def_levels, const uint8_t* d_rep
   const bool one_pass = any_out && bounded;
   hipError_t e = one_pass ? emit() : pqg::launch_assemble(s, dl, rl, n_slots, P, counts, n_blocks, totals, ticket, 0);
   uint64_t* h_tot = (uint64_t*)ctx->pin_err.p;
-  if (e == hipSuccess) e = hipMemcpyAsync(h_tot, totals, sizeof(uint64_t) * pqg::ASM_MAX_DEPTHS, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_tot, totals, sizeof(uint64_t) * pqg::ASM_TOTAL_WORDS, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
     set_status(st, PQG_ERR_HIP, -1, -1, hipGetErrorString(e));
     return PQG_ERR_HIP;
   }
-  if (h_tot[pqg::ASM_MAX_DEPTHS - 1] == ~0ull) {  // a look-back wait timed out (k_asm_onepass)
+  // a look-back wait timed out (k_asm_onepass; the count pass leaves the flag word as it was)
+  if (one_pass && h_tot[pqg::ASM_TIMEOUT_WORD] == ~0ull) {
     set_status(st, PQG_ERR_TIMEOUT, -1, -1, "assembly look-back");
     return PQG_ERR_TIMEOUT;
   }
@@ -1446,10 +1447,16 @@ int pqg_assemble(pqg_ctx* ctx, const uint8_t* d_def_levels, const uint8_t* d_rep
   }
   if (!any_out || one_pass) return PQG_OK;  // counts only, or already emitted
   e = emit();
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(h_tot + pqg::ASM_TIMEOUT_WORD, totals + pqg::ASM_TIMEOUT_WORD, sizeof(uint64_t), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) {
     set_status(st, PQG_ERR_HIP, -1, -1, hipGetErrorString(e));
     return PQG_ERR_HIP;
+  }
+  if (h_tot[pqg::ASM_TIMEOUT_WORD] == ~0ull) {
+    set_status(st, PQG_ERR_TIMEOUT, -1, -1, "assembly look-back");
+    return PQG_ERR_TIMEOUT;
   }
   return PQG_OK;
 }

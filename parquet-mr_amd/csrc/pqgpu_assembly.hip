@@ -221,7 +221,8 @@ __global__ __launch_bounds__(ASM1_THREADS) void k_asm_onepass(const uint8_t* __r
         __builtin_amdgcn_s_sleep(1);
         // bounded (2 s of s_memrealtime): a block that never publishes leaves a wrong count, not a hang
         if (__builtin_amdgcn_s_memrealtime() - t_wait > 200000000ull) {
-          if (lane == 0) totals[ASM_MAX_DEPTHS - 1] = ~0ull;  // flagged to the host as a timeout
+          // flagged to the host as a timeout, in a word of its own (the last block stores every depth's total)
+          if (lane == 0) totals[ASM_TIMEOUT_WORD] = ~0ull;
           break;
         }
         continue;

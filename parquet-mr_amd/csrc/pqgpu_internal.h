@@ -138,6 +138,10 @@ hipError_t launch_bin_copy(hipStream_t st, const uint8_t* bytes, uint64_t n_byte
 // pqgpu_assembly.hip: levels -> offsets / validity of one leaf column's path
 constexpr uint32_t ASM_MAX_DEPTHS = 8;  // repetition depths 0..7 (max_rep <= 7)
 constexpr uint32_t ASM_MAX_NODES = 16;  // path length
+// 64-bit words at `totals`: the entry counts of depths 0..7, the ticket (its low half), then the look-back
+// timeout flag in a word of its own (~0 when a wait timed out): with max_rep == 7 every count word is in use
+constexpr uint32_t ASM_TIMEOUT_WORD = ASM_MAX_DEPTHS + 1;
+constexpr uint32_t ASM_TOTAL_WORDS = ASM_MAX_DEPTHS + 2;
 struct AsmParams {
   uint32_t n_nodes;
   uint32_t max_rep;
