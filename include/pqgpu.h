@@ -41,7 +41,9 @@
  * PQG_FILTER_DICT_LDS_BYTES) and pqg_decode_dictionary; record selection on repeated columns
  * (pqg_take_record_column, pqg_take_record_counts, pqg_take_records); record filters on INT96 and
  * FIXED_LEN_BYTE_ARRAY columns and the three binary comparators (pqg_filter_binary_order,
- * pqg_filter_column_type, pqg_filter_create_typed).
+ * pqg_filter_column_type, pqg_filter_create_typed); page checksums on the device (pqg_crc_job,
+ * pqg_crc32_pages, pqg_crc32_sync, PQG_DISPATCH_CRC_TILE_BYTES) with the host helpers pqg_crc32_combine
+ * and pqg_crc_jobs_from_headers.
  * ABI 5: record-level filter2 predicates over decoded columns (pqg_filter_create /
  * pqg_filter_program / pqg_filter_destroy on the host, pqg_filter_run on the device).
  * ABI 4: pqg_page_desc carries the V2 header's num_nulls
@@ -263,6 +265,8 @@ void* pqg_ctx_stream(pqg_ctx* ctx);
  *   PQG_DISPATCH_ZSTD_PREPASS    pqg_zstd_decompress: 1 = lane-per-page sequence pre-pass + replay (default),
  *                                0 = every page takes the inline sequence decoder (the pre-pass's
  *                                fallback); applies to later pqg_zstd_decompress calls
+ *   PQG_DISPATCH_CRC_TILE_BYTES  pqg_crc32_pages: bytes of a range one wave checksums: 4096, 8192, 16384
+ *                                or 32768 (default PQG_CRC_TILE_BYTES); applies to later calls
  * Returns PQG_ERR_INVALID_ARG for an unknown key or value. Not thread-safe (like the ctx). */
 enum pqg_dispatch {
   PQG_DISPATCH_PLAIN_ONE_PASS = 1,
@@ -271,7 +275,8 @@ enum pqg_dispatch {
   PQG_DISPATCH_DICT_FUSED = 4,
   PQG_DISPATCH_NULL_HINTS = 5,
   PQG_DISPATCH_TAKE_STAGED = 6,
-  PQG_DISPATCH_ZSTD_PREPASS = 7
+  PQG_DISPATCH_ZSTD_PREPASS = 7,
+  PQG_DISPATCH_CRC_TILE_BYTES = 8
 };
 int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value);
 
@@ -1060,6 +1065,57 @@ typedef struct pqg_take_record_counts {
 int pqg_take_records(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, const pqg_take_record_column* cols,
                      int n_cols, uint64_t out_rows_capacity, pqg_take_record_counts* d_counts,
                      pqg_take_result* d_result);
+
+/* ---- page checksums (an addition to ABI 6) ----------------------------------------------------------
+ * ParquetFileReader.Chunk.readAllPages -> verifyCrc (ParquetFileReader.java:1805-1813): with
+ * parquet.page.verify-checksum.enabled the CRC-32 of a page's bytes as they sit in the file (V2: the
+ * level sections and the data together, :1925-1931) is compared with PageHeader.crc before anything
+ * else touches the page. pqg_crc32_pages computes the checksums of many byte ranges of one device
+ * buffer, the same bytes the codec kernels or pqg_decode read afterwards.
+ *
+ * CRC-32 is linear over GF(2): a range splits into tiles of PQG_CRC_TILE_BYTES whose partial values
+ * are computed independently (one wave per tile) and folded per job by a second launch. No workgroup
+ * waits on another and there are no atomics. */
+#define PQG_CRC_TILE_BYTES 32768    /* bytes of a range one wave checksums (the fastest of 4, 8, 16 and
+                                       32 KiB: DESIGN.md §3); PQG_DISPATCH_CRC_TILE_BYTES */
+#define PQG_CRC_VERIFY 1            /* pqg_crc_job.flags: compare with `expected` */
+
+typedef struct pqg_crc_job {        /* sizeof == 24 */
+  uint64_t offset;    /* first byte of the checksummed range in d_bytes, any alignment */
+  uint32_t size;      /* bytes; 0 is valid (CRC 0) */
+  uint32_t expected;  /* PageHeader.crc as an unsigned 32-bit value */
+  uint32_t flags;     /* PQG_CRC_* */
+  uint32_t reserved;  /* 0 */
+} pqg_crc_job;
+
+/* d_crc[j] (device, n_jobs, may be NULL) <- java.util.zip.CRC32 of d_bytes[offset, offset + size) of
+ * job j (the reflected polynomial 0xEDB88320: what pqg_crc32 and zlib's crc32 compute); d_status[j]
+ * (device, n_jobs) <- PQG_OK, or PQG_ERR_CRC when the job has PQG_CRC_VERIFY and the value differs from
+ * `expected` (an unsigned comparison, as verifyCrc masks with 0xffffffffL). Asynchronous on the ctx
+ * stream. `jobs` is a HOST array (its sizes come from page headers the host parsed); it is copied
+ * before the call returns, through growable pinned memory of the ctx. Jobs are independent: they may
+ * overlap, repeat and come in any order, and bytes outside a job's range never influence its result.
+ * d_bytes is 4-byte aligned and readable up to n_bytes rounded up to 4; no load leaves that range.
+ * PQG_ERR_INVALID_ARG, before any launch: NULL ctx; n_jobs < 0; NULL jobs, d_bytes or d_status with
+ * n_jobs > 0; a job with offset + size > n_bytes; non-zero reserved; unknown flags.
+ * PQG_ERR_UNSUPPORTED: more than 2^28 tiles in one call. n_jobs == 0 is valid and launches nothing.
+ * Launches: two (per-tile partials, per-job fold), whatever n_jobs is. */
+int pqg_crc32_pages(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, const pqg_crc_job* jobs, int n_jobs,
+                    uint32_t* d_crc, int32_t* d_status);
+/* Synchronises the ctx stream and reads d_status back, like the codec *_sync calls: the first failing
+ * job is st->page, and the message of a mismatch contains "CRC checksum verification failed". */
+int pqg_crc32_sync(pqg_ctx* ctx, const int32_t* d_status, int n_jobs, pqg_status* st);
+
+/* Host only. zlib's crc32_combine: crc(A || B) from crc(A), crc(B) and the length of B (len_b == 0:
+ * crc_a ^ crc_b, which zlib's identity gives). For a caller that checksums a page in pieces. */
+uint32_t pqg_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* Host only. The verifying jobs of a framed chunk (pqg_frame_chunk's headers): every header with
+ * has_crc (dictionary page, V1, V2) becomes a job over chunk_offset + body_offset,
+ * compressed_page_size bytes, with PQG_CRC_VERIFY and the header's crc; header_of_job[j] (may be NULL)
+ * is the header's index. *n_jobs = jobs needed; capacity too small: PQG_ERR_INVALID_ARG with
+ * st->value_index = the count needed (as pqg_frame_chunk). */
+int pqg_crc_jobs_from_headers(const pqg_page_header* headers, int n_headers, uint64_t chunk_offset, pqg_crc_job* jobs,
+                              int32_t* header_of_job, int capacity, int* n_jobs, pqg_status* st);
 
 /* Human-readable name of an error code. */
 const char* pqg_error_name(int code);

@@ -22,6 +22,7 @@
 #include "pqgpu_internal.h"
 #include "pqgpu_filter.h"
 #include "pqgpu_take.h"
+#include "pqgpu_crc.h"
 
 using pqg::ColumnDev;
 using pqg::PageWork;
@@ -228,6 +229,17 @@ struct pqg_ctx {
   hipEvent_t take_ev[TAKE_SLOTS] = {};
   uint32_t take_seq = 0;
   bool take_staged = true;  // PQG_DISPATCH_TAKE_STAGED
+  // pqg_crc32_pages: the constants of crc_tile on the device (built at the first call and when the tile
+  // size changes), and per slot the job + tile tables in growable pinned memory, their device copy and
+  // the tiles' partial values (a slot is reused once the fold that read it has run: its event)
+  static constexpr int CRC_SLOTS = 2;
+  uint32_t crc_tile = PQG_CRC_TILE_BYTES;  // PQG_DISPATCH_CRC_TILE_BYTES
+  uint32_t crc_tab_tile = 0;
+  DevBuf crc_tab;
+  PinnedBuf crc_pin[CRC_SLOTS];
+  DevBuf crc_dev[CRC_SLOTS], crc_partial[CRC_SLOTS];
+  hipEvent_t crc_ev[CRC_SLOTS] = {};
+  uint32_t crc_seq = 0;
 };
 
 extern "C" {
@@ -320,6 +332,10 @@ int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value) {
       if (value != 0 && value != 1) return PQG_ERR_INVALID_ARG;
       ctx->zstd_prepass = value != 0;
       return PQG_OK;
+    case PQG_DISPATCH_CRC_TILE_BYTES:
+      if (value < 0 || !pqg::crc_tile_ok((uint32_t)value)) return PQG_ERR_INVALID_ARG;
+      ctx->crc_tile = (uint32_t)value;
+      return PQG_OK;
     default: return PQG_ERR_INVALID_ARG;
   }
 }
@@ -355,6 +371,13 @@ int pqg_ctx_destroy(pqg_ctx* c) {
   c->take_pin.release();
   for (hipEvent_t& e : c->take_ev)
     if (e) (void)hipEventDestroy(e);
+  c->crc_tab.release();
+  for (int i = 0; i < pqg_ctx::CRC_SLOTS; i++) {
+    c->crc_pin[i].release();
+    c->crc_dev[i].release();
+    c->crc_partial[i].release();
+    if (c->crc_ev[i]) (void)hipEventDestroy(c->crc_ev[i]);
+  }
   if (c->copy_stream) {
     (void)hipStreamSynchronize(c->copy_stream);
     (void)hipStreamDestroy(c->copy_stream);
@@ -1768,6 +1791,65 @@ int pqg_take_records(pqg_ctx* ctx, const uint64_t* d_bitmap, uint64_t n_rows, co
                                                 (uint32_t)n_cols, plan, out_rows_capacity, (uint64_t*)ctx->take_scratch.p,
                                                 d_counts, d_result, ctx->take_staged);
   return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+// ---- page checksums (pqgpu_crc_host.cpp validates and builds the tables, pqgpu_crc.hip runs) ---------
+int pqg_crc32_pages(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, const pqg_crc_job* jobs, int n_jobs,
+                    uint32_t* d_crc, int32_t* d_status) {
+  uint64_t n_tiles = 0;
+  const uint32_t T = ctx ? ctx->crc_tile : (uint32_t)PQG_CRC_TILE_BYTES;
+  const int rc = pqg::crc_validate(ctx != nullptr, d_bytes, n_bytes, jobs, n_jobs, d_status, T, &n_tiles);
+  if (rc != PQG_OK || n_jobs == 0) return rc;
+  if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
+  if (ctx->crc_tab_tile != T) {  // the constants of this tile size (a pageable copy: done when it returns)
+    std::vector<uint32_t> tab(pqg::crc_table_words(T));
+    pqg::crc_build_tables(T, tab.data());
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || ctx->crc_tab.ensure(4 * tab.size()) != hipSuccess ||
+        hipMemcpy(ctx->crc_tab.p, tab.data(), 4 * tab.size(), hipMemcpyHostToDevice) != hipSuccess)
+      return PQG_ERR_HIP;
+    ctx->crc_tab_tile = T;
+  }
+  const uint32_t slot = ctx->crc_seq++ % pqg_ctx::CRC_SLOTS;
+  hipEvent_t& ev = ctx->crc_ev[slot];
+  if (!ev) {
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return PQG_ERR_HIP;
+  } else if (hipEventSynchronize(ev) != hipSuccess) {  // the fold of this slot CRC_SLOTS calls ago
+    return PQG_ERR_HIP;
+  }
+  const size_t job_bytes = sizeof(pqg::CrcJobDev) * (size_t)n_jobs;  // a multiple of 8: the tiles follow
+  const size_t bytes = job_bytes + sizeof(pqg::CrcTile) * (size_t)n_tiles;
+  // grown by half again, so that a run of calls with rising page counts does not reallocate each time
+  if (ctx->crc_pin[slot].cap < bytes && ctx->crc_pin[slot].ensure(bytes + bytes / 2) != hipSuccess) return PQG_ERR_HIP;
+  if (ctx->crc_dev[slot].cap < bytes && ctx->crc_dev[slot].ensure(bytes + bytes / 2) != hipSuccess) return PQG_ERR_HIP;
+  if (ctx->crc_partial[slot].cap < 4 * (size_t)n_tiles &&
+      ctx->crc_partial[slot].ensure(6 * (size_t)n_tiles) != hipSuccess)
+    return PQG_ERR_HIP;
+  uint8_t* pin = (uint8_t*)ctx->crc_pin[slot].p;
+  pqg::crc_build(jobs, n_jobs, T, (pqg::CrcJobDev*)pin, (pqg::CrcTile*)(pin + job_bytes));
+  if (hipMemcpyAsync(ctx->crc_dev[slot].p, pin, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return PQG_ERR_HIP;
+  const uint8_t* dev = (const uint8_t*)ctx->crc_dev[slot].p;
+  const hipError_t e = pqg::launch_crc(ctx->stream, d_bytes, n_bytes, (const pqg::CrcTile*)(dev + job_bytes), (uint32_t)n_tiles,
+                                       (const pqg::CrcJobDev*)dev, (uint32_t)n_jobs, (const uint32_t*)ctx->crc_tab.p, T,
+                                       (uint32_t*)ctx->crc_partial[slot].p, d_crc, d_status);
+  if (e != hipSuccess || hipEventRecord(ev, ctx->stream) != hipSuccess) return PQG_ERR_HIP;
+  return PQG_OK;
+}
+
+int pqg_crc32_sync(pqg_ctx* ctx, const int32_t* d_status, int n_jobs, pqg_status* st) {
+  if (!ctx || n_jobs < 0) return PQG_ERR_INVALID_ARG;
+  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return PQG_ERR_HIP;
+  if (st) set_status(st, PQG_OK, -1, -1, "crc32");
+  if (!d_status || n_jobs == 0) return PQG_OK;
+  std::vector<int32_t> h((size_t)n_jobs);
+  if (hipMemcpy(h.data(), d_status, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyDeviceToHost) != hipSuccess)
+    return PQG_ERR_HIP;
+  for (int j = 0; j < n_jobs; j++)
+    if (h[(size_t)j]) {
+      set_status(st, h[(size_t)j], j, -1,
+                 h[(size_t)j] == PQG_ERR_CRC ? "could not verify page integrity, CRC checksum verification failed" : "crc32 job");
+      return h[(size_t)j];
+    }
+  return PQG_OK;
 }
 
 static_assert(sizeof(pqg_snappy_job) == 24, "pqg_snappy_job layout");

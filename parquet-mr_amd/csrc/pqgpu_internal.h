@@ -196,6 +196,13 @@ uint64_t take_records_scratch_words(uint64_t max_rows, uint32_t n_cols, uint64_t
 hipError_t launch_take_records(hipStream_t st, const uint64_t* bitmap, uint64_t n_rows, const TakeRecDev* d_recs,
                                uint32_t n_cols, const TakeRecPlan& plan, uint64_t rows_capacity, uint64_t* scratch,
                                pqg_take_record_counts* counts, pqg_take_result* result, bool staged);
+// pqgpu_crc.hip: pqg_crc32_pages (CrcTile, CrcJobDev, the constants `tab` of tile_bytes: pqgpu_crc.h).
+// partial: n_tiles words; k_crc_tiles (skipped without tiles), then k_crc_fold
+struct CrcTile;
+struct CrcJobDev;
+hipError_t launch_crc(hipStream_t st, const uint8_t* bytes, uint64_t n_bytes, const CrcTile* tiles, uint32_t n_tiles,
+                      const CrcJobDev* jobs, uint32_t n_jobs, const uint32_t* tab, uint32_t tile_bytes,
+                      uint32_t* partial, uint32_t* crc, int32_t* status);
 hipError_t launch_unpack_runs(hipStream_t st, int w, const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
                               const uint32_t* counts, const uint64_t* out_off, int32_t* out, int n_runs,
                               uint32_t max_count);

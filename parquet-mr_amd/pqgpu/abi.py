@@ -223,6 +223,7 @@ DISPATCH_GZIP_PREPASS_MIN = 3  # pqg_gzip_decompress: smallest page (output byte
 DISPATCH_DICT_FUSED = 4  # dictionary pages: 1 = walk + expansion in one launch, 0 = two launches
 DISPATCH_TAKE_STAGED = 6  # pqg_take: 1 = kept elements staged in LDS and stored as aligned full-wave runs, 0 = one store per kept lane
 DISPATCH_ZSTD_PREPASS = 7  # pqg_zstd_decompress: 1 = sequence pre-pass + replay, 0 = every page through the inline decoder
+DISPATCH_CRC_TILE_BYTES = 8  # pqg_crc32_pages: bytes of a range one wave checksums (4096, 8192, 16384, 32768)
 DISPATCH_NULL_HINTS = 5  # V2 nullable columns: 1 = value kernels from the header null counts (verified), 0 = levels first
 
 
@@ -330,3 +331,18 @@ class TakeRecordCounts(C.Structure):
 
 
 assert C.sizeof(TakeRecordColumn) == 128 and C.sizeof(TakeRecordCounts) == 32
+
+
+# ---- page checksums (include/pqgpu.h, "page checksums") ----------------------------------------------
+CRC_TILE_BYTES = 32768  # PQG_CRC_TILE_BYTES
+CRC_VERIFY = 1          # pqg_crc_job.flags: compare with `expected`
+
+
+class CrcJob(C.Structure):
+    """pqg_crc_job (24 bytes): one checksummed byte range of a device buffer."""
+    _fields_ = [("offset", C.c_uint64), ("size", C.c_uint32), ("expected", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+CRC_JOB_DTYPE = np.dtype([("offset", "<u8"), ("size", "<u4"), ("expected", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert C.sizeof(CrcJob) == CRC_JOB_DTYPE.itemsize == 24

@@ -31,6 +31,9 @@ class Page:
     # uncompressed_page_size (V2: levels included).
     codec: int = 0
     uncompressed_size: int = 0
+    # PageHeader.crc as an unsigned 32-bit value: the CRC-32 of `body` as it sits in the file (V2: the
+    # levels and the data together); None: the header carries none (pageHeader.isSetCrc())
+    crc: Optional[int] = None
 
 
 @dataclass
@@ -52,6 +55,7 @@ class ColumnChunk:
     # CorruptDeltaByteArrays.requiresSequentialReads(created_by, DELTA_BYTE_ARRAY): build_batch flags
     # the chunk's DELTA_BYTE_ARRAY pages after its first page PQG_PAGE_DBA_CARRY
     dba_carry: bool = False
+    dict_crc: Optional[int] = None    # the dictionary page header's crc (unsigned), None: not set
 
     @property
     def num_slots(self):

@@ -160,9 +160,53 @@ class Decoder:
                  batch.LZ4_RAW: ("pqg_lz4_raw_decompress", "pqg_lz4_raw_sync", "lz4_raw block"),
                  batch.GZIP: ("pqg_gzip_decompress", "pqg_gzip_sync", "gzip stream")}
 
-    def upload_chunks(self, chunks):
+    def crc32(self, d_bytes, offsets, sizes, expected=None):
+        """CRC-32 (java.util.zip.CRC32) of the byte ranges [offsets[j], offsets[j] + sizes[j]) of the device
+        uint8 tensor d_bytes, by pqg_crc32_pages; with `expected` (unsigned values) every job verifies.
+        Returns (crcs_tensor, status_codes, status); the tensor is int32 on the device and holds the bits of the
+        unsigned values (`.cpu().numpy().view(np.uint32)`)."""
+        n = len(offsets)
+        table = np.zeros(n, dtype=abi.CRC_JOB_DTYPE)
+        table["offset"], table["size"] = offsets, sizes
+        if expected is not None:
+            table["expected"], table["flags"] = expected, abi.CRC_VERIFY
+        d_crc = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        d_status = torch.full((max(n, 1),), -1, dtype=torch.int32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        L = native.lib()
+        native.check(L.pqg_crc32_pages(self.ctx, d_bytes.data_ptr(), d_bytes.numel(), table.ctypes.data if n else None, n,
+                                       d_crc.data_ptr(), d_status.data_ptr()), what="pqg_crc32_pages")
+        st = abi.Status()
+        L.pqg_crc32_sync(self.ctx, d_status.data_ptr(), n, C.byref(st))
+        return d_crc[:n], d_status[:n].cpu().numpy(), st
+
+    def _verify_crc(self, buffers):
+        """buffers: [(device tensor, [(offset, size, crc, key)])]; key = (chunk, page in the chunk, or -1 for
+        its dictionary page). Raises PqgError(ERR_CRC) for the first failing page in chunk / page order."""
+        bad = []
+        for d_bytes, jobs in buffers:
+            if not jobs:
+                continue
+            _, codes, st = self.crc32(d_bytes, [j[0] for j in jobs], [j[1] for j in jobs], [j[2] for j in jobs])
+            if st.code not in (abi.OK, abi.ERR_CRC):
+                native.check(st.code, st, what="pqg_crc32_pages")
+            bad += [jobs[i][3] for i in np.flatnonzero(codes)]
+        if bad:
+            ci, k = min(bad)
+            what = (f"chunk {ci}, dictionary page: could not verify dictionary page integrity" if k < 0 else
+                    f"chunk {ci}, page {k}: could not verify page integrity") + ", CRC checksum verification failed"
+            raise native.PqgError(abi.ERR_CRC, what=what)
+
+    def upload_chunks(self, chunks, verify_crc=False):
         """Column chunks whose pages may be SNAPPY-, GZIP-, ZSTD- or LZ4_RAW-compressed -> a DeviceBatch of
         uncompressed pages.
+
+        verify_crc: every page and dictionary page that carries a crc (batch.Page.crc, ColumnChunk.dict_crc) is
+        checksummed on the device from the bytes that were uploaded (pqg_crc32_pages) before anything is
+        decompressed, as ParquetFileReader.Chunk.readAllPages verifies before it hands a page on; a mismatch
+        raises PqgError(ERR_CRC) naming the chunk and the page. A compressed V2 page's checksum covers its
+        levels and its compressed data, so with verification on its whole body goes into the codec's source
+        buffer (the data section still starts on a 16-byte boundary there).
 
         The batch is laid out for the uncompressed pages (batch.build_batch over placeholders of
         the uncompressed sizes), the compressed blocks are uploaded once, and
@@ -171,57 +215,85 @@ class Decoder:
         Raises PqgError(CORRUPT / EOF) with the failing block when a block is malformed or its
         length differs from the header."""
         import copy
-        placeholders, blocks = [], []   # (codec, payload, ("dict", chunk) | ("page", page index), prefix)
+        # (codec, payload, ("dict", chunk) | ("page", page index), prefix, levels kept before the payload in
+        #  the codec source, (crc, (chunk, page | -1)) | None)
+        placeholders, blocks = [], []
+        plain_crcs = []                 # uncompressed pages with a crc: (("dict", chunk) | ("page", page index), crc, key)
         n_page = 0
-        for ch in chunks:
+        for ci, ch in enumerate(chunks):
             ph = copy.copy(ch)
             ph.pages = []
+            dcrc = ch.dict_crc if verify_crc else None
             if ch.dict_page is not None and ch.dict_codec != batch.UNCOMPRESSED:
                 if ch.dict_codec not in self._CODEC_FN:
                     raise native.PqgError(abi.ERR_UNSUPPORTED, what=f"dictionary page codec {ch.dict_codec}")
                 ph.dict_page = bytes(ch.dict_uncompressed_size)
-                blocks.append((ch.dict_codec, ch.dict_page, ("dict", len(placeholders)), 0))
-            for pg in ch.pages:
+                blocks.append((ch.dict_codec, ch.dict_page, ("dict", len(placeholders)), 0, b"",
+                               None if dcrc is None else (dcrc, (ci, -1))))
+            elif ch.dict_page is not None and dcrc is not None:
+                plain_crcs.append((("dict", len(placeholders)), dcrc, (ci, -1)))
+            for k, pg in enumerate(ch.pages):
                 q = copy.copy(pg)
+                crc = pg.crc if verify_crc else None
                 if pg.codec in self._CODEC_FN:
                     lv = pg.rl_byte_length + pg.dl_byte_length if pg.version == 2 else 0
                     q.body = pg.body[:lv] + bytes(pg.uncompressed_size - lv)
-                    blocks.append((pg.codec, pg.body[lv:], ("page", n_page), lv))
+                    blocks.append((pg.codec, pg.body[lv:], ("page", n_page), lv, b"" if crc is None else pg.body[:lv],
+                                   None if crc is None else (crc, (ci, k))))
                 elif pg.codec != batch.UNCOMPRESSED:
                     raise native.PqgError(abi.ERR_UNSUPPORTED, what=f"page codec {pg.codec}")
+                elif crc is not None:
+                    plain_crcs.append((("page", n_page), crc, (ci, k)))
                 ph.pages.append(q)
                 n_page += 1
             placeholders.append(ph)
         hb = batch.build_batch(placeholders)
         dbatch = DeviceBatch(hb, self.device)
-        if not blocks:
-            return dbatch
         col_of_chunk = []
         seen = {}
         for i, ch in enumerate(placeholders):
             seen.setdefault(getattr(ch, "column_index", i), len(seen))
             col_of_chunk.append(seen[getattr(ch, "column_index", i)])
+        crc_buffers = []                # [(device tensor, [(offset, size, crc, key)])]
+        if plain_crcs:
+            jobs = []
+            for (kind, idx), crc, key in plain_crcs:
+                if kind == "dict":
+                    jobs.append((int(hb.columns[col_of_chunk[idx]]["dict_offset"]), len(placeholders[idx].dict_page), crc, key))
+                else:
+                    jobs.append((int(hb.pages["offset"][idx]), int(hb.pages["size"][idx]), crc, key))
+            crc_buffers.append((dbatch.bytes, jobs))
+        if not blocks:
+            self._verify_crc(crc_buffers)
+            return dbatch
         jobsets = []
         for codec in sorted({b[0] for b in blocks}):
             mine = [b for b in blocks if b[0] == codec]
             src, pos = [], 0
             table = np.zeros(len(mine), dtype=np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"),
                                                         ("src_size", "<u4"), ("dst_size", "<u4")]))
-            for j, (_, payload, (kind, idx), prefix) in enumerate(mine):
+            crc_jobs = []
+            for j, (_, payload, (kind, idx), prefix, levels, crc) in enumerate(mine):
                 if kind == "dict":
                     dst = int(hb.columns[col_of_chunk[idx]]["dict_offset"])
                     n_out = int(hb.columns[col_of_chunk[idx]]["dict_size"])
                 else:
                     dst = int(hb.pages["offset"][idx]) + prefix
                     n_out = int(hb.pages["size"][idx]) - prefix
-                table[j] = (pos, dst, len(payload), n_out)
-                src.append(payload + bytes((-len(payload)) % 16))
+                # a checksummed V2 page: its levels sit right before the payload, which stays 16-byte aligned
+                front = bytes((-len(levels)) % 16) + levels
+                if crc is not None:
+                    crc_jobs.append((pos + len(front) - len(levels), len(levels) + len(payload), crc[0], crc[1]))
+                table[j] = (pos + len(front), dst, len(payload), n_out)
+                src.append(front + payload + bytes((-len(payload)) % 16))
                 pos += len(src[-1])
             d_src = torch.from_numpy(np.frombuffer(b"".join(src) + bytes(16), dtype=np.uint8).copy()).to(self.device)
             d_jobs = torch.from_numpy(table.view(np.uint8).copy()).to(self.device)
             d_status = torch.zeros(len(mine), dtype=torch.int32, device=self.device)
             jobsets.append((codec, d_src, d_jobs, d_status, len(mine)))
+            crc_buffers.append((d_src, crc_jobs))
         torch.cuda.current_stream(self.device).synchronize()  # the uploads above, before the decoder's stream
+        self._verify_crc(crc_buffers)  # before the codecs' outcome: the reference throws in readAllPages
         dbatch.codec_jobs = jobsets
         self.decompress(dbatch)
         for codec, _, _, d_status, n in jobsets:

@@ -177,8 +177,10 @@ def read_column_chunk(buf, start, length, physical_type, max_def=0, max_rep=0, t
         if len(data) != size:
             raise ThriftError("page body truncated")
         t = h["type"]
+        crc = h["crc"] & 0xFFFFFFFF if "crc" in h else None  # verifyCrc masks with 0xffffffffL
         if t == DICTIONARY_PAGE:
             chunk.dict_page = data
+            chunk.dict_crc = crc
             chunk.dict_num_values = h["num_values"]
             chunk.dict_encoding = h["encoding"]
             if codec:
@@ -187,7 +189,7 @@ def read_column_chunk(buf, start, length, physical_type, max_def=0, max_rep=0, t
             chunk.pages.append(Page(body=data, num_values=h["num_values"], encoding=h["encoding"], version=1,
                                     rl_encoding=h["repetition_level_encoding"],
                                     dl_encoding=h["definition_level_encoding"], codec=codec,
-                                    uncompressed_size=usize if codec else 0))
+                                    uncompressed_size=usize if codec else 0, crc=crc))
             seen += h["num_values"]
         elif t == DATA_PAGE_V2:
             compressed = bool(codec) and h.get("is_compressed", True)
@@ -195,7 +197,8 @@ def read_column_chunk(buf, start, length, physical_type, max_def=0, max_rep=0, t
                                     rl_byte_length=h["repetition_levels_byte_length"],
                                     dl_byte_length=h["definition_levels_byte_length"],
                                     num_nulls=h.get("num_nulls", 0), num_rows=h.get("num_rows", 0),
-                                    codec=codec if compressed else 0, uncompressed_size=usize if compressed else 0))
+                                    codec=codec if compressed else 0, uncompressed_size=usize if compressed else 0,
+                                    crc=crc))
             seen += h["num_values"]
         pos = body + size
     return chunk

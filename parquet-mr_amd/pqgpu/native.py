@@ -42,6 +42,8 @@ EXPORTS = [
     "pqg_take",
     # ... with repeated columns: whole records
     "pqg_take_records",
+    # page checksums on the device, and their host helpers
+    "pqg_crc32_pages", "pqg_crc32_sync", "pqg_crc32_combine", "pqg_crc_jobs_from_headers",
 ]
 
 
@@ -120,6 +122,11 @@ def lib():
         L.pqg_decode_dictionary.argtypes = [vp, vp, u64, vp, C.POINTER(abi.Status)]
         L.pqg_take.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
         L.pqg_take_records.argtypes = [vp, vp, u64, vp, i32, u64, vp, vp]
+        L.pqg_crc32_pages.argtypes = [vp, vp, u64, vp, i32, vp, vp]
+        L.pqg_crc32_sync.argtypes = [vp, vp, i32, C.POINTER(abi.Status)]
+        L.pqg_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, u64]
+        L.pqg_crc32_combine.restype = C.c_uint32
+        L.pqg_crc_jobs_from_headers.argtypes = [vp, i32, u64, vp, vp, i32, C.POINTER(i32), C.POINTER(abi.Status)]
         L.pqg_error_name.argtypes = [i32]
         L.pqg_error_name.restype = C.c_char_p
         if L.pqg_abi_version() != abi.ABI_VERSION:
