@@ -18,8 +18,6 @@ struct ErrCount {
   uint32_t* p;
   uint32_t epoch;
 };
-constexpr uint32_t ERR_EPOCH_MAX = 0xFFFFu;
-constexpr uint64_t ERR_KEY_MASK = (1ull << 48) - 1;
 
 hipError_t launch_dict(int width, hipStream_t st, const uint8_t* bytes, uint64_t n_bytes, PageWork* work,
                        const ColumnDev* cols, const int32_t* list, int n, uint64_t* rec, uint32_t* chunk_run,

@@ -139,6 +139,11 @@ enum Cls { C_DICT4 = 0, C_DICT8, C_IDS, C_PLAIN, C_BOOL, C_DELTA4, C_DELTA8, C_B
            C_DDG, C_NCLS };
 constexpr int N_DICT_CLS = 3;  // C_DICT4, C_DICT8, C_IDS: run-record walk + chunk expansion
 
+// Error words (pqg::ErrCount, pqgpu_internal.h): (launch epoch << 48) | (~key & ERR_KEY_MASK), epochs
+// 1..ERR_EPOCH_MAX
+constexpr uint32_t ERR_EPOCH_MAX = 0xFFFFu;
+constexpr uint64_t ERR_KEY_MASK = (1ull << 48) - 1;
+
 struct HostErr {
   int page;
   int kind;  // 0 init, 2 value

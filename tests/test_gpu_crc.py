@@ -16,6 +16,7 @@ import thrift_compact
 from helpers import assert_same
 from pqgpu import abi, framing, native
 from test_crc_host import jobs_from_headers, raw_chunk, written_chunks
+from test_gpu_take import busy_stream
 from tools.synth import writer
 
 pytestmark = pytest.mark.gpu
@@ -103,6 +104,31 @@ def test_many_tiles(decoder):
     for (_, size), c in zip(rows[1:], crcs[1:]):
         chained = native.lib().pqg_crc32_combine(chained, int(c), size)
     assert chained == int(crcs[0])
+
+
+def test_slot_reuse_in_queued_calls(decoder):
+    """2 * CRC_SLOTS + 1 calls of pqg_crc32_pages queued on one context with no wait between them, each with a job
+    list of its own: one job of T + 1 bytes (two tiles and a fold) at its own offset. The job and tile tables go
+    up through a pinned slot that the call CRC_SLOTS later reuses: a slot overwritten before the fold that reads
+    it has run shows as a call that gave another call's checksum."""
+    calls, size = 5, T + 1
+    buf = np.random.default_rng(5).integers(0, 256, size=calls * (size + 3) + 8, dtype=np.uint8).tobytes()
+    tables = [job_table([(k * (size + 3) + k % 4, size)]) for k in range(calls)]
+    d_bytes = upload(decoder, buf)
+    d_crc = [torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device=decoder.device) for _ in range(calls)]
+    d_status = [torch.full((1,), -7, dtype=torch.int32, device=decoder.device) for _ in range(calls)]
+    held = busy_stream(decoder)
+    L = native.lib()
+    for t, c, s in zip(tables, d_crc, d_status):
+        assert L.pqg_crc32_pages(decoder.ctx, d_bytes.data_ptr(), d_bytes.numel(), t.ctypes.data, 1, c.data_ptr(),
+                                 s.data_ptr()) == abi.OK
+    st = abi.Status()
+    for s in d_status:
+        assert L.pqg_crc32_sync(decoder.ctx, s.data_ptr(), 1, C.byref(st)) == abi.OK
+    want = [int(want_crcs(buf, t)[0]) for t in tables]
+    assert len(set(want)) == calls
+    assert [int(c.cpu().numpy().view(np.uint32)[0]) for c in d_crc] == want
+    del held
 
 
 def test_isolation(decoder):

@@ -20,6 +20,7 @@ from pqgpu import abi, native
 from pqgpu import decoder as D
 from pqgpu import filter as F
 from test_gpu_filter import POISON64, draw_values, random_levels, run, set_members
+from test_gpu_take import busy_stream
 from test_gpu_take import check as check_take
 from tools.synth import writer
 
@@ -508,6 +509,43 @@ def test_filter_then_take_without_a_sync(decoder, mains):
     kept_rows = keep & d.ref[I64].valid(N_MAIN)
     dense = np.cumsum(d.ref[I64].valid(N_MAIN)) - 1
     assert np.array_equal(np.asarray(d.ids[I64].dictionary.numpy())[kept_ids], np.asarray(d.ref[I64].values)[dense[kept_rows]])
+
+
+# ---- the pinned dictionary-table slots -----------------------------------------------------------------------------
+
+def test_slot_reuse_in_queued_calls(decoder):
+    """2 * FILTER_DICT_SLOTS + 1 calls of pqg_filter_run_dict queued on one context with no wait between them: one
+    filter, one id column of 256 rows, a dictionary of 4 entries that differs from call to call (entry j lies
+    below the literal in call k when bit j of k + 1 is set). The dictionary table goes up through a pinned slot
+    that the call FILTER_DICT_SLOTS later reuses: a slot overwritten before the copy out of it has run shows as
+    a call that selected by another call's dictionary."""
+    n, calls = 256, 9
+    rng = np.random.default_rng(92)
+    ids = rng.integers(0, 4, size=n).astype(np.uint32)
+    assert set(ids) == {0, 1, 2, 3}
+    pred = F.lt(F.col(0), 50)
+    cols, refs = [], []
+    for k in range(calls):
+        entries = np.array([1 if (k + 1) >> j & 1 else 100 for j in range(4)], dtype=np.int32)
+        raw = np.concatenate([entries, np.full(4, 0x5A5A5A5A, dtype=np.int32)]).view(np.uint8)
+        d = D.DeviceColumn(abi.INT32, torch.from_numpy(raw).to(decoder.device))
+        d.n_values = 4
+        cols.append(hand_column(decoder, abi.INT32, ids, None, 0, d))
+        refs.append(R.RefColumn(abi.INT32, entries[ids], None, 0))
+    flt = F.Filter(pred, [cols[0]])
+    held = busy_stream(decoder)
+    runs = [run(decoder, flt, [c], n) for c in cols]
+    seen = set()
+    for (words, _, sel), ref in zip(runs, refs):
+        want = R.evaluate(pred, [ref], n)
+        assert sel.count == int(want.sum())
+        got = words.cpu().numpy()
+        assert np.array_equal(got[:n // 64].view(np.uint64), R.bitmap_words(want))
+        assert (got[n // 64:] == POISON64).all()
+        assert np.array_equal(sel.row_ids.cpu().numpy(), np.flatnonzero(want))
+        seen.add(want.tobytes())
+    assert len(seen) == calls  # every call has an answer of its own
+    del held
 
 
 # ---- decode_dictionary -------------------------------------------------------------------------------------------------

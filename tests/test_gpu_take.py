@@ -126,6 +126,17 @@ def check_outputs(dev, ref, outs, keep, counts):
     return want
 
 
+def busy_stream(dec, passes=24):
+    """A few milliseconds of work on the decoder's stream, so that calls queued right behind it are all made
+    before the first of them runs. Returns the tensor it works on: keep it until the stream has been waited for."""
+    x = torch.zeros(1 << 27, dtype=torch.float32, device=dec.device)
+    dec.stream.wait_stream(torch.cuda.current_stream(dec.device))
+    with torch.cuda.stream(dec.stream):
+        for _ in range(passes):
+            x.add_(1.0)
+    return x
+
+
 def check(dec, dev, ref, keep, selection=None, garbage_tail=False):
     """One take into poisoned outputs, compared with the reference; returns (taken, outputs, reference outcome)."""
     n = len(keep)
@@ -488,3 +499,27 @@ def test_direct_store_variant(decoder, main, binary):
         check(decoder, binary[0], binary[1], binary_masks(binary[2])["runs"])
     finally:
         decoder.set_dispatch(abi.DISPATCH_TAKE_STAGED, 1)
+
+
+# ---- the pinned table slots ------------------------------------------------------------------------------------
+
+def test_slot_reuse_in_queued_calls(decoder):
+    """2 * TAKE_SLOTS + 1 calls queued on one context with no wait between them, each with a bitmap and output
+    tensors of its own. A call's column table goes up through a pinned slot that the call TAKE_SLOTS later
+    reuses: a slot overwritten before the copy out of it has run shows as a call that wrote into another
+    call's outputs and left its own poisoned."""
+    n, calls = 256, 9
+    rng = np.random.default_rng(91)
+    vals = rng.integers(-2**31, 2**31 - 1, size=n, dtype=np.int32)
+    col = device_column(abi.INT32, torch.from_numpy(vals).to(decoder.device))
+    ref = [R.RefColumn(abi.INT32, vals, None, 0)]
+    keeps = [rng.random(n) < 0.5 for _ in range(calls)]
+    assert len({k.tobytes() for k in keeps}) == calls
+    bitmaps = [bitmap_tensor(decoder, k) for k in keeps]
+    outs = [outputs(decoder, [col], n) for _ in range(calls)]
+    held = busy_stream(decoder)
+    taken = [decoder.take(b, [col], n_rows=n, out=o) for b, o in zip(bitmaps, outs)]
+    for keep, o, t in zip(keeps, outs, taken):
+        assert t.n_rows == int(keep.sum())
+        check_outputs([col], ref, o, keep, t.counts)
+    del held
