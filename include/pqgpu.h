@@ -929,6 +929,108 @@ int pqg_filter_run_records(pqg_ctx* ctx, const pqg_filter* filter, const pqg_fil
  * stay alive until then. */
 int pqg_decode_dictionary(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_column_desc* col, pqg_status* st);
 
+/* pqg_decode_dictionary for n dictionary pages of one buffer in one plan (an addition to ABI 6): cols[i] names
+ * dictionary page i, with its own type and its own output buffers. The checks, the error codes, values_written
+ * after pqg_sync and the capacity contract are those of pqg_decode_dictionary, per entry; st->page is the index
+ * of the failing dictionary (a descriptor error: the first such entry, and nothing is launched). `cols` must
+ * stay alive until pqg_sync. n == 0 is valid and launches nothing. The number of launches does not depend on n:
+ * the pages are the n required one-page columns of one plan, whose PLAIN BYTE_ARRAY pages take one wave each
+ * (the form PQG_DISPATCH_PLAIN_ONE_PASS = 3 selects, which waits on no other workgroup), whatever the ctx's
+ * dispatch setting says. The dictionary pages of every row group of a file can so be decoded before any data
+ * page is uploaded (pqg_filter_row_groups, below). */
+int pqg_decode_dictionaries(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_column_desc* cols, int n,
+                            pqg_status* st);
+
+/* ---- row-group dictionary filter (an addition to ABI 6) -------------------------------------------
+ * Before a reader with a predicate reads anything it asks which row groups it has to read at all
+ * (RowGroupFilter.visit(FilterPredicateCompat), filter2/compat/RowGroupFilter.java:100-115). Its
+ * dictionary level is DictionaryFilter.canDrop (filter2/dictionarylevel/DictionaryFilter.java): a row
+ * group is dropped when every data page of the column is dictionary-encoded and no dictionary entry can
+ * satisfy the predicate. pqg_filter_row_groups answers that for all row groups of a file in one call;
+ * what a dropped row group holds is then never uploaded. StatisticsFilter and BloomFilterImpl, the other
+ * two levels, are host-only metadata work and not part of this.
+ *
+ * Host only. DictionaryFilter.hasNonDictionaryPages (DictionaryFilter.java:561-589) over a chunk's
+ * ColumnMetaData.encoding_stats (`stats`, n_stats entries; n_stats < 0: the chunk has none) and its
+ * `encodings` list. With stats they are converted as ParquetMetadataConverter.convertEncodingStats does
+ * (:689-709): the encodings of DATA_PAGE and DATA_PAGE_V2 entries form the data set, an entry with count
+ * 0 included; DICTIONARY_PAGE entries are ignored. Then EncodingStats.hasNonDictionaryEncodedPages
+ * (EncodingStats.java:77-94) with its short circuit: RLE_DICTIONARY is removed first and PLAIN_DICTIONARY
+ * only if RLE_DICTIONARY was absent, so a chunk that lists both returns 1; an empty data set returns 0.
+ * Without stats: PLAIN_DICTIONARY must be among `encodings` and nothing else but RLE and BIT_PACKED,
+ * otherwise 1 (a chunk with RLE_DICTIONARY only returns 1). Returns 0 or 1. */
+typedef struct pqg_page_encoding_stat { int32_t page_type, encoding, count; } pqg_page_encoding_stat; /* sizeof == 12 */
+int pqg_chunk_has_non_dictionary_pages(const pqg_page_encoding_stat* stats, int n_stats, /* < 0: no encoding_stats */
+                                       const int32_t* encodings, int n_encodings);
+
+/* What the host knows of one column chunk of one row group. */
+#define PQG_RG_MISSING            1  /* the file has no such column (meta == null) */
+#define PQG_RG_NO_DICTIONARY      2  /* no dictionary page was read (expandDictionary returns null) */
+#define PQG_RG_NON_DICT_PAGES     4  /* pqg_chunk_has_non_dictionary_pages */
+#define PQG_RG_MAY_CONTAIN_NULL   8  /* statistics absent, num_nulls unset or > 0 */
+typedef struct pqg_rowgroup_column {     /* sizeof == 32; entry [g * n_cols + c] of a host table */
+  pqg_filter_dictionary dict;            /* decoder layout, device pointers, as for pqg_filter_run_dict */
+  uint32_t flags; uint32_t reserved;     /* PQG_RG_*; reserved == 0 */
+} pqg_rowgroup_column;
+/* Device-resident outcome of one pqg_filter_row_groups. */
+typedef struct pqg_rowgroup_result {     /* sizeof == 16 */
+  uint64_t n_kept;      /* row groups that might match, whatever kept_capacity is */
+  int32_t error;        /* PQG_OK (no launch of this call reports an error of its own today) */
+  int32_t error_group;  /* -1 */
+} pqg_rowgroup_result;
+
+/* DictionaryFilter.canDrop for n_row_groups row groups. The predicate is the filter's rewritten program,
+ * which has no NOT: what RowGroupFilter passes after LogicalInverseRewriter. Filters with contains are
+ * accepted. `cols` is a host table of n_row_groups * n_cols entries (n_cols: the filter's); only the
+ * columns the predicate names are read. Asynchronous on the ctx stream; every output is a DEVICE pointer.
+ * d_drop_bitmap: ceil(n_row_groups / 64) words, bit g set when row group g cannot match, the bits past
+ * n_row_groups 0. d_kept_ids (may be NULL): the kept groups ascending, the first kept_capacity of them.
+ * n_row_groups == 0 is valid.
+ *
+ * The dictionary of a (row group, column) is "usable" when none of MISSING, NO_DICTIONARY, NON_DICT_PAGES
+ * is set and the column's type is INT32, INT64, FLOAT, DOUBLE, BYTE_ARRAY or FIXED_LEN_BYTE_ARRAY; BOOLEAN
+ * and INT96 never drop (expandDictionary, DictionaryFilter.java:91-131). any(L): leaf L holds on at least
+ * one dictionary entry taken as a present value. A leaf CANNOT match when:
+ *   eq(null), in with null in the set        never (:136-141, :384-390)
+ *   notEq(null)                              the column is MISSING (:177-181)
+ *   notIn whose set is exactly {null}        the column is MISSING (:446-450)
+ *   notIn with null among other members      never (:452-456)
+ *   eq lt ltEq gt gtEq in (non-null literal) MISSING, or the dictionary is usable and not any(L)
+ *                                            (:143-169, :218-380, :392-437)
+ *   notEq(v)                                 usable, n_entries >= 1, not any(L), MAY_CONTAIN_NULL clear: every
+ *                                            entry equals v (dictSet.size() == 1 && contains, :183-215)
+ *   notIn(S), no null in S                   usable, not any(L), MAY_CONTAIN_NULL clear (:458-489; MISSING
+ *                                            gives MIGHT_MATCH)
+ * so an empty usable dictionary cannot match eq, in, the ordering leaves and notIn, and might match notEq.
+ * Duplicate entries change nothing (the reference compares against a HashSet). `and` cannot match if either
+ * side cannot, `or` only if both cannot (:496-504, the inverted and / or of a "can drop" visitor),
+ * contains(L) takes L's verdict (Operators.java:459-461, DictionaryFilter.java:492-494); the root's verdict
+ * is the drop bit.
+ * Equality is equals(), not the comparator: eq, notEq, in and notIn go through HashSet.contains. For a
+ * Binary that is byte equality whatever the column's order: a DECIMAL on BYTE_ARRAY stored as 00 01 does
+ * not equal the literal 01 here though pqg_filter_run says it does, and FLOAT16 NaNs with different
+ * payloads differ. For FLOAT and DOUBLE equals() is the comparator's equality (one NaN, -0.0 != 0.0). So
+ * the row-group form of the program keys the equality leaves of binary columns by their unsigned bytes
+ * (sets of more than 8 members re-sorted for the binary search); ordering leaves keep the comparator.
+ *
+ * Refused before any launch, PQG_ERR_INVALID_ARG: a NULL ctx, filter or d_result; n_row_groups > 0 without
+ * cols or d_drop_bitmap; n_cols different from the filter's; non-zero `reserved` or unknown flags in a
+ * column the predicate names; a usable BYTE_ARRAY dictionary with entries but without binary_data, or any
+ * usable dictionary with entries but without values; more than 2^31 - 1 row groups or 2^26 work items
+ * (a work item is PQG_RG_TILE_ENTRIES entries of one dictionary).
+ * No load leaves [0, n_entries) of a dictionary or, for BYTE_ARRAY, [offsets[0], offsets[n_entries]) of
+ * its bytes (offsets are clamped).
+ * Launches, none of which waits on another workgroup, without atomics, and whose number does not depend
+ * on n_row_groups or n_cols: k_rg_any (a wave per (row group, column, tile of PQG_RG_TILE_ENTRIES entries)
+ * of a host-built work list, every leaf of the column on one load of the entry; a hit stores 1 into the
+ * (row group, leaf) flag, zeroed in the stream beforehand), k_rg_fold (a lane per row group: the program
+ * over the flags, the bitmap word by ballot, the kept count per word), the scan of those counts with the
+ * result, and the kept ids. */
+#define PQG_RG_TILE_ENTRIES 1024
+int pqg_filter_row_groups(pqg_ctx* ctx, const pqg_filter* filter, const pqg_rowgroup_column* cols, int n_cols,
+                          uint64_t n_row_groups, uint64_t* d_drop_bitmap, int64_t* d_kept_ids,
+                          uint64_t kept_capacity, pqg_rowgroup_result* d_result);
+
 /* ---- row selection ------------------------------------------------------------------------------
  * The last step of decode -> filter -> records: the rows a bitmap keeps, gathered into compact
  * columns in the decoder's own layout. What is reproduced is what the reference hands back after a

@@ -632,6 +632,13 @@ int pqg_sync(pqg_ctx* ctx, pqg_status* st) {
       prc = dict_page_eof_code(P, *ctx->dict_user);
       set_status(&pst, prc, -1, pst.value_index, "dictionary page");
     }
+    // pqg_decode_dictionaries: page i is dictionary i
+    const bool dict_batch = P == ctx->last && ctx->dicts_user && ctx->last_cols == ctx->dicts_desc.data();
+    if (prc == PQG_ERR_EOF && dict_batch && pst.page >= 0 && pst.page < P->L.n_pages &&
+        ctx->dicts_desc[(size_t)pst.page].physical_type == PQG_BYTE_ARRAY) {
+      prc = dict_page_eof_code(P, ctx->dicts_user[pst.page]);
+      set_status(&pst, prc, pst.page, pst.value_index, "dictionary page");
+    }
     if (prc != PQG_OK && pst.code == 0 && pst.message[0] == '\0')
       set_status(&pst, prc, -1, -1, prc == PQG_ERR_HIP ? hipGetErrorString(hipGetLastError()) : "plan sync failed");
     if (prc != PQG_OK && rc == PQG_OK) {
@@ -650,6 +657,8 @@ int pqg_sync(pqg_ctx* ctx, pqg_status* st) {
         ctx->last_cols[i].values_written = n;
       }
       if (ctx->dict_user && ctx->last_cols == &ctx->dict_desc) ctx->dict_user->values_written = ctx->dict_desc.values_written;
+      if (dict_batch)
+        for (int i = 0; i < P->L.n_cols; i++) ctx->dicts_user[i].values_written = ctx->dicts_desc[(size_t)i].values_written;
     }
   }
   ctx->unsynced.clear();
@@ -695,6 +704,7 @@ int pqg::decode_impl(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, uin
     }
   }
   ctx->dict_user = nullptr;
+  ctx->dicts_user = nullptr;
   if (ctx->last) {
     pqg_plan_destroy(ctx->last);
     ctx->last = nullptr;
@@ -724,44 +734,89 @@ int pqg_decode(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_colum
   return pqg::decode_impl(ctx, d_bytes, n_bytes, n_bytes, cols, n_cols, pages, n_pages, d_page_value_counts, st);
 }
 
+// The checks pqg_decode makes of a column's dictionary page, in its order (PlainValuesDictionary).
+static int dict_page_check(const pqg_column_desc& col, uint64_t n_bytes) {
+  const int ew = elem_width(col.physical_type, col.type_length);
+  if (col.dict_offset < 0) return PQG_ERR_NO_DICTIONARY;
+  if (col.dict_encoding != PQG_PLAIN && col.dict_encoding != PQG_PLAIN_DICTIONARY) return PQG_ERR_DICT_ENCODING;
+  if (col.physical_type == PQG_FIXED_LEN_BYTE_ARRAY && col.type_length <= 0) return PQG_ERR_CORRUPT;
+  if ((uint64_t)col.dict_offset + col.dict_size > n_bytes) return PQG_ERR_INVALID_ARG;
+  if (col.physical_type == PQG_BOOLEAN ? ((uint64_t)col.dict_num_values + 7) / 8 > col.dict_size
+                                       : ew > 0 && (uint64_t)col.dict_num_values * (uint64_t)ew > col.dict_size)
+    return PQG_ERR_EOF;
+  return PQG_OK;
+}
+
+// A dictionary page is the PLAIN values of a required column: V1 page `g` of column `column` of a batch, whose
+// descriptor `d` is the caller's without levels, flags and dictionary.
+static void dict_page_as_column(const pqg_column_desc& col, int column, pqg_column_desc* d, pqg_page_desc* g) {
+  *d = col;
+  d->max_rep = d->max_def = 0;
+  d->dict_offset = -1;
+  d->dict_size = d->dict_num_values = 0;
+  d->flags = 0;
+  d->def_levels = d->rep_levels = nullptr;
+  d->levels_capacity = 0;
+  d->values_written = 0;
+  std::memset(g, 0, sizeof(*g));
+  g->offset = (uint64_t)col.dict_offset;
+  g->size = col.dict_size;
+  g->num_values = col.dict_num_values;
+  g->column = column;
+  g->version = 1;
+  g->encoding = PQG_PLAIN;
+  g->rl_encoding = g->dl_encoding = PQG_RLE;
+}
+
 int pqg_decode_dictionary(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_column_desc* col, pqg_status* st) {
   if (st) { std::memset(st, 0, sizeof(*st)); st->page = -1; }
   if (!ctx || !col) return PQG_ERR_INVALID_ARG;
-  int err = PQG_OK;
-  const int ew = elem_width(col->physical_type, col->type_length);
-  // the checks pqg_decode makes of a column's dictionary page, in its order (PlainValuesDictionary)
-  if (col->dict_offset < 0) err = PQG_ERR_NO_DICTIONARY;
-  else if (col->dict_encoding != PQG_PLAIN && col->dict_encoding != PQG_PLAIN_DICTIONARY) err = PQG_ERR_DICT_ENCODING;
-  else if (col->physical_type == PQG_FIXED_LEN_BYTE_ARRAY && col->type_length <= 0) err = PQG_ERR_CORRUPT;
-  else if ((uint64_t)col->dict_offset + col->dict_size > n_bytes) err = PQG_ERR_INVALID_ARG;
-  else if (col->physical_type == PQG_BOOLEAN ? ((uint64_t)col->dict_num_values + 7) / 8 > col->dict_size
-                                             : ew > 0 && (uint64_t)col->dict_num_values * (uint64_t)ew > col->dict_size)
-    err = PQG_ERR_EOF;
+  const int err = dict_page_check(*col, n_bytes);
   if (err) {
     set_status(st, err, -1, -1, "dictionary page");
     return err;
   }
-  // a dictionary page is the PLAIN values of a required column: one V1 page of a one-column batch
-  pqg_column_desc& d = ctx->dict_desc;
-  d = *col;
-  d.max_rep = d.max_def = 0;
-  d.dict_offset = -1;
-  d.dict_size = d.dict_num_values = 0;
-  d.flags = 0;
-  d.def_levels = d.rep_levels = nullptr;
-  d.levels_capacity = 0;
-  d.values_written = 0;
   pqg_page_desc g;
-  std::memset(&g, 0, sizeof(g));
-  g.offset = (uint64_t)col->dict_offset;
-  g.size = col->dict_size;
-  g.num_values = col->dict_num_values;
-  g.column = 0;
-  g.version = 1;
-  g.encoding = PQG_PLAIN;
-  g.rl_encoding = g.dl_encoding = PQG_RLE;
-  const int rc = pqg::decode_impl(ctx, d_bytes, n_bytes, n_bytes, &d, 1, &g, 1, nullptr, st);
+  dict_page_as_column(*col, 0, &ctx->dict_desc, &g);
+  const int rc = pqg::decode_impl(ctx, d_bytes, n_bytes, n_bytes, &ctx->dict_desc, 1, &g, 1, nullptr, st);
   if (rc == PQG_OK) ctx->dict_user = col;  // pqg_sync hands values_written on
+  return rc;
+}
+
+int pqg_decode_dictionaries(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, pqg_column_desc* cols, int n,
+                            pqg_status* st) {
+  if (st) { std::memset(st, 0, sizeof(*st)); st->page = -1; }
+  if (!ctx || n < 0 || (n > 0 && !cols)) return PQG_ERR_INVALID_ARG;
+  if (n == 0) return PQG_OK;
+  for (int i = 0; i < n; i++) {
+    const int err = dict_page_check(cols[i], n_bytes);
+    if (err) {
+      set_status(st, err, i, -1, "dictionary page");
+      return err;
+    }
+    // the capacity contract of pqg_decode_dictionary, per dictionary (decode_impl makes the same check per
+    // column, after this one has passed)
+    const uint64_t need = (uint64_t)cols[i].dict_num_values + (bin_out(cols[i]) ? 1 : 0);  // offsets[n + 1]
+    if (need > cols[i].values_capacity || (need && !cols[i].values)) {
+      set_status(st, PQG_ERR_INVALID_ARG, i, i, "output capacity");
+      return PQG_ERR_INVALID_ARG;
+    }
+  }
+  // the descriptors of an earlier batch are about to go: nothing may point at them any more (a batch that
+  // was never synchronised loses its values_written, not its memory safety)
+  ctx->dicts_user = nullptr;
+  if (ctx->last_cols == ctx->dicts_desc.data()) ctx->last_cols = nullptr;
+  // one plan of n required one-page columns. Its PLAIN BYTE_ARRAY pages take one wave each
+  // (PQG_DISPATCH_PLAIN_ONE_PASS = 3: k_bin_plain_pg, which follows a page from its start and waits on nothing);
+  // the tile form's look-back orders tiles over the whole grid, which n short pages do not need
+  ctx->dicts_desc.assign((size_t)n, pqg_column_desc{});
+  std::vector<pqg_page_desc> pages((size_t)n);
+  for (int i = 0; i < n; i++) dict_page_as_column(cols[i], i, &ctx->dicts_desc[(size_t)i], &pages[(size_t)i]);
+  const int plain_mode = ctx->plain_mode;
+  ctx->plain_mode = 3;
+  const int rc = pqg::decode_impl(ctx, d_bytes, n_bytes, n_bytes, ctx->dicts_desc.data(), n, pages.data(), n, nullptr, st);
+  ctx->plain_mode = plain_mode;
+  if (rc == PQG_OK) ctx->dicts_user = cols;  // pqg_sync hands values_written on
   return rc;
 }
 

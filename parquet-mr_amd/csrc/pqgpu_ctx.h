@@ -241,10 +241,22 @@ struct pqg_ctx {
   pqg::DevBuf filter_dict;
   pqg::PinnedBuf filter_dict_pin;
   pqg::SlotRing<FILTER_DICT_SLOTS> filter_dict_ring;
+  // pqg_filter_row_groups: the device image of the row-group form of the filter uploaded last (by its serial);
+  // per slot the column table + work list in growable pinned memory, their device copy, and the hit flags and
+  // per-word counts (a slot is reused once the launches that read it have run: rg_ring)
+  static constexpr int RG_SLOTS = 2;
+  pqg::DevBuf rg_image;
+  uint64_t rg_serial = 0;
+  pqg::PinnedBuf rg_pin[RG_SLOTS];
+  pqg::DevBuf rg_dev[RG_SLOTS], rg_scratch[RG_SLOTS];
+  pqg::SlotRing<RG_SLOTS> rg_ring;
   // pqg_decode_dictionary: the one-column batch it decodes (last_cols points at dict_desc until the next
   // decode) and the caller's descriptor that pqg_sync fills from it
   pqg_column_desc dict_desc = {};
   pqg_column_desc* dict_user = nullptr;
+  // pqg_decode_dictionaries: the same for a batch of n dictionary pages, one column each
+  std::vector<pqg_column_desc> dicts_desc;
+  pqg_column_desc* dicts_user = nullptr;
   // pqg_take: per-tile counts; the column table on the device and the pinned slots it is copied from
   // (a slot is reused once the copy out of it has run: take_ring)
   static constexpr int TAKE_SLOTS = 4;

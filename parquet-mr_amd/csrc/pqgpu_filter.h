@@ -32,6 +32,8 @@ constexpr uint8_t FILTER_DEV_SIGNED = 0x04;   // PQG_FILTER_ORDER_SIGNED_INTEGER
 constexpr uint8_t FILTER_DEV_FLOAT16 = 0x08;  // PQG_FILTER_ORDER_FLOAT16
 constexpr uint8_t FILTER_DEV_KEY128 = 0x10;   // with FILTER_DEV_SIGNED: literals carry 128-bit keys
 constexpr uint32_t FILTER_KEY128_BYTES = 16;  // the widest value the 128-bit keys compare
+// pqg_filter::rg_image only (the row-group form of the program): a notIn whose set is exactly {null}
+constexpr uint8_t FILTER_DEV_NULL_ONLY = 0x20;
 
 // Header of the device image: FilterDevHeader, nodes[n_nodes], order[PQG_FILTER_MAX_NODES] (u8: the
 // leaves grouped by slot, then nothing), cells[n_cells] (8 bytes each), bytes[n_bytes] padded to 8 + 8.
@@ -144,6 +146,11 @@ struct pqg_filter {
   std::vector<uint8_t> bytes;           // BYTE_ARRAY literal bytes
   std::vector<int32_t> slot_column;     // slot -> column index
   std::vector<uint8_t> image;           // device image (FilterDevHeader ...)
+  // pqg_filter_row_groups: the image with the equality leaves (eq, notEq, in, notIn) of binary columns keyed by
+  // their unsigned bytes, whatever the column's order (HashSet.contains is equals(), not the comparator), their
+  // sets of more than 8 members sorted that way, and FILTER_DEV_NULL_ONLY
+  std::vector<uint8_t> rg_image;
+  std::vector<uint8_t> null_only;       // per program node: in / notIn whose set is exactly {null}
   bool has_contains = false;            // a CONTAINS node: pqg_filter_run_records only
 };
 

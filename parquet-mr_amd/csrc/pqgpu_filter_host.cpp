@@ -139,6 +139,105 @@ int contains_rewrite(const std::vector<pqg_filter_node>& p, int i, int* code, in
   return col[0];
 }
 
+// The device image of the created filter `f` (FilterDevHeader ...). equals = false: the filter's own, every
+// leaf under its column's comparator. equals = true: pqg_filter::rg_image, the form pqg_filter_row_groups runs.
+void build_image(const pqg_filter* f, bool equals, std::vector<uint8_t>* out) {
+  const uint8_t* lb = f->bytes.data();
+  // the image's cells, leaf by leaf: one per literal, or three under FILTER_DEV_KEY128 (every literal of the
+  // leaf fits 16 bytes once its redundant sign bytes are gone, and so does every value it can meet below the
+  // byte-wise path) while cells and bytes together stay inside what the limits give an image
+  std::vector<uint64_t> img_cells;
+  std::vector<uint32_t> img_begin(f->program.size(), 0);
+  std::vector<uint8_t> dev_flags(f->program.size(), 0);
+  size_t spare = (8u * PQG_FILTER_MAX_LITERALS + PQG_FILTER_MAX_LITERAL_BYTES - 8u * f->cells.size() - f->bytes.size()) / 16u;
+  std::vector<uint64_t> by_bytes;
+  for (size_t i = 0; i < f->program.size(); i++) {
+    const pqg_filter_node& nd = f->program[i];
+    if (!is_leaf(nd.op)) continue;
+    const pqg_filter_column_type& ct = f->columns[(size_t)nd.column];
+    const int type = ct.physical_type;
+    const uint64_t* raw = f->cells.data() + nd.literal_begin;
+    img_begin[i] = (uint32_t)img_cells.size();
+    if (equals && nd.op == PQG_FILTER_NOTIN && f->null_only[i]) dev_flags[i] |= pqg::FILTER_DEV_NULL_ONLY;
+    const bool equality = nd.op == PQG_FILTER_EQ || nd.op == PQG_FILTER_NOTEQ || nd.op == PQG_FILTER_IN || nd.op == PQG_FILTER_NOTIN;
+    if (equals && equality && is_binary(type) && ct.binary_order != PQG_FILTER_ORDER_UNSIGNED_BYTES) {
+      // Binary.equals: the bytes and the length, under every comparator; the set was sorted by the comparator
+      by_bytes.assign(raw, raw + nd.n_literals);
+      if (nd.n_literals > pqg::FILTER_IN_LINEAR)
+        std::sort(by_bytes.begin(), by_bytes.end(), [lb](uint64_t x, uint64_t y) {
+          return compare_bytes(lb + (uint32_t)x, (uint32_t)(x >> 32), lb + (uint32_t)y, (uint32_t)(y >> 32)) < 0;
+        });
+      img_cells.insert(img_cells.end(), by_bytes.begin(), by_bytes.end());
+    } else if (ct.binary_order == PQG_FILTER_ORDER_FLOAT16) {
+      dev_flags[i] |= pqg::FILTER_DEV_FLOAT16;
+      for (uint32_t k = 0; k < nd.n_literals; k++) img_cells.push_back((uint64_t)float16_key(lb, raw[k]));
+    } else if (ct.binary_order == PQG_FILTER_ORDER_SIGNED_INTEGER) {
+      dev_flags[i] |= pqg::FILTER_DEV_SIGNED;
+      const uint32_t width = type == PQG_INT96 ? 12u : (uint32_t)ct.type_length;
+      bool keys = nd.n_literals <= spare && (type == PQG_BYTE_ARRAY || width <= pqg::FILTER_KEY128_BYTES);
+      int64_t hi;
+      uint64_t lo;
+      for (uint32_t k = 0; keys && k < nd.n_literals; k++)
+        keys = pqg::filter_key128(lb + (uint32_t)raw[k], (uint32_t)(raw[k] >> 32), &hi, &lo);
+      if (keys) {
+        dev_flags[i] |= pqg::FILTER_DEV_KEY128;
+        spare -= nd.n_literals;
+      }
+      for (uint32_t k = 0; k < nd.n_literals; k++) {
+        img_cells.push_back(raw[k]);
+        if (!keys) continue;
+        (void)pqg::filter_key128(lb + (uint32_t)raw[k], (uint32_t)(raw[k] >> 32), &hi, &lo);
+        img_cells.push_back((uint64_t)hi);
+        img_cells.push_back(lo);
+      }
+    } else {
+      for (uint32_t k = 0; k < nd.n_literals; k++)
+        img_cells.push_back(is_binary(type) ? raw[k]
+                                            : (uint64_t)pqg::filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, raw[k]));
+    }
+  }
+  pqg::FilterDevHeader h{};
+  h.n_nodes = (uint32_t)f->program.size();
+  h.n_slots = (uint32_t)f->slot_column.size();
+  h.n_cells = (uint32_t)img_cells.size();
+  h.n_bytes = (uint32_t)f->bytes.size();
+  h.cells_off = (uint32_t)(sizeof(h) + h.n_nodes * sizeof(pqg::FilterDevNode) + PQG_FILTER_MAX_NODES);
+  h.bytes_off = h.cells_off + 8u * h.n_cells;
+  h.image_bytes = h.bytes_off + (h.n_bytes + 7u) / 8u * 8u + 8u;
+  out->assign(h.image_bytes, 0);
+  uint8_t* img = out->data();
+  uint8_t* order = img + sizeof(h) + h.n_nodes * sizeof(pqg::FilterDevNode);
+  for (uint32_t s = 0; s < h.n_slots; s++)
+    for (uint32_t i = 0; i < h.n_nodes; i++) {
+      const pqg_filter_node& nd = f->program[i];
+      if (is_leaf(nd.op) && nd.column == f->slot_column[s]) order[h.n_leaves++] = (uint8_t)i;
+    }
+  std::vector<char> contained(h.n_nodes, 0);
+  for (const pqg_filter_node& nd : f->program)
+    if (nd.op == PQG_FILTER_CONTAINS) contained[(size_t)nd.left] = 1;
+  for (uint32_t i = 0; i < h.n_nodes; i++) {
+    const pqg_filter_node& nd = f->program[i];
+    pqg::FilterDevNode d{};
+    d.op = (uint8_t)nd.op;
+    d.flags = (uint8_t)(nd.flags | dev_flags[i] | (contained[i] ? pqg::FILTER_DEV_CONTAINED : 0u));
+    if (is_leaf(nd.op)) {
+      const pqg_filter_column_type& ct = f->columns[(size_t)nd.column];
+      d.type = (uint8_t)ct.physical_type;
+      d.slot = (uint8_t)(std::find(f->slot_column.begin(), f->slot_column.end(), nd.column) - f->slot_column.begin());
+      d.n_lit = (uint16_t)nd.n_literals;
+      d.lit_begin = img_begin[i];
+      d.width = ct.physical_type == PQG_INT96 ? 12u : ct.physical_type == PQG_FIXED_LEN_BYTE_ARRAY ? (uint32_t)ct.type_length : 0u;
+    } else {
+      d.left = (uint8_t)nd.left;
+      d.right = (uint8_t)(nd.right < 0 ? 0 : nd.right);
+    }
+    memcpy(img + sizeof(h) + i * sizeof(d), &d, sizeof(d));
+  }
+  if (h.n_cells) memcpy(img + h.cells_off, img_cells.data(), 8u * h.n_cells);
+  if (h.n_bytes) memcpy(img + h.bytes_off, lb, h.n_bytes);
+  memcpy(img, &h, sizeof(h));
+}
+
 // pqg_filter_create (`bare`: the columns came as plain physical types, INT96 / FLBA are refused) and
 // pqg_filter_create_typed: one validation path.
 int create_filter(const pqg_filter_node* nodes, int n_nodes, const pqg_filter_column_type* columns, int n_cols, bool bare,
@@ -253,6 +352,7 @@ int create_filter(const pqg_filter_node* nodes, int n_nodes, const pqg_filter_co
     orig.push_back(i);
     if (inv[(size_t)i]) nd.op = inverse(nd.op);
     nd.reserved = 0;
+    f->null_only.push_back(is_leaf(nd.op) && (nd.flags & PQG_FILTER_NULL_LITERAL) && nd.n_literals == 0);
     if (is_leaf(nd.op)) {
       const uint32_t begin = (uint32_t)f->cells.size();
       for (uint32_t k = 0; k < nd.n_literals; k++) f->cells.push_back(literals[nd.literal_begin + k]);
@@ -317,88 +417,8 @@ int create_filter(const pqg_filter_node* nodes, int n_nodes, const pqg_filter_co
     if (std::find(f->slot_column.begin(), f->slot_column.end(), nd.column) == f->slot_column.end())
       f->slot_column.push_back(nd.column);
   }
-  // the image's cells, leaf by leaf: one per literal, or three under FILTER_DEV_KEY128 (every literal of the
-  // leaf fits 16 bytes once its redundant sign bytes are gone, and so does every value it can meet below the
-  // byte-wise path) while cells and bytes together stay inside what the limits give an image
-  std::vector<uint64_t> img_cells;
-  std::vector<uint32_t> img_begin(f->program.size(), 0);
-  std::vector<uint8_t> dev_flags(f->program.size(), 0);
-  size_t spare = (8u * PQG_FILTER_MAX_LITERALS + PQG_FILTER_MAX_LITERAL_BYTES - 8u * f->cells.size() - f->bytes.size()) / 16u;
-  for (size_t i = 0; i < f->program.size(); i++) {
-    const pqg_filter_node& nd = f->program[i];
-    if (!is_leaf(nd.op)) continue;
-    const pqg_filter_column_type& ct = f->columns[(size_t)nd.column];
-    const int type = ct.physical_type;
-    const uint64_t* raw = f->cells.data() + nd.literal_begin;
-    img_begin[i] = (uint32_t)img_cells.size();
-    if (ct.binary_order == PQG_FILTER_ORDER_FLOAT16) {
-      dev_flags[i] = pqg::FILTER_DEV_FLOAT16;
-      for (uint32_t k = 0; k < nd.n_literals; k++) img_cells.push_back((uint64_t)float16_key(lb, raw[k]));
-    } else if (ct.binary_order == PQG_FILTER_ORDER_SIGNED_INTEGER) {
-      dev_flags[i] = pqg::FILTER_DEV_SIGNED;
-      const uint32_t width = type == PQG_INT96 ? 12u : (uint32_t)ct.type_length;
-      bool keys = nd.n_literals <= spare && (type == PQG_BYTE_ARRAY || width <= pqg::FILTER_KEY128_BYTES);
-      int64_t hi;
-      uint64_t lo;
-      for (uint32_t k = 0; keys && k < nd.n_literals; k++)
-        keys = pqg::filter_key128(lb + (uint32_t)raw[k], (uint32_t)(raw[k] >> 32), &hi, &lo);
-      if (keys) {
-        dev_flags[i] |= pqg::FILTER_DEV_KEY128;
-        spare -= nd.n_literals;
-      }
-      for (uint32_t k = 0; k < nd.n_literals; k++) {
-        img_cells.push_back(raw[k]);
-        if (!keys) continue;
-        (void)pqg::filter_key128(lb + (uint32_t)raw[k], (uint32_t)(raw[k] >> 32), &hi, &lo);
-        img_cells.push_back((uint64_t)hi);
-        img_cells.push_back(lo);
-      }
-    } else {
-      for (uint32_t k = 0; k < nd.n_literals; k++)
-        img_cells.push_back(is_binary(type) ? raw[k]
-                                            : (uint64_t)pqg::filter_key(type, (nd.flags & PQG_FILTER_UNSIGNED) != 0, raw[k]));
-    }
-  }
-  pqg::FilterDevHeader h{};
-  h.n_nodes = (uint32_t)f->program.size();
-  h.n_slots = (uint32_t)f->slot_column.size();
-  h.n_cells = (uint32_t)img_cells.size();
-  h.n_bytes = (uint32_t)f->bytes.size();
-  h.cells_off = (uint32_t)(sizeof(h) + h.n_nodes * sizeof(pqg::FilterDevNode) + PQG_FILTER_MAX_NODES);
-  h.bytes_off = h.cells_off + 8u * h.n_cells;
-  h.image_bytes = h.bytes_off + (h.n_bytes + 7u) / 8u * 8u + 8u;
-  f->image.assign(h.image_bytes, 0);
-  uint8_t* img = f->image.data();
-  uint8_t* order = img + sizeof(h) + h.n_nodes * sizeof(pqg::FilterDevNode);
-  for (uint32_t s = 0; s < h.n_slots; s++)
-    for (uint32_t i = 0; i < h.n_nodes; i++) {
-      const pqg_filter_node& nd = f->program[i];
-      if (is_leaf(nd.op) && nd.column == f->slot_column[s]) order[h.n_leaves++] = (uint8_t)i;
-    }
-  std::vector<char> contained(h.n_nodes, 0);
-  for (const pqg_filter_node& nd : f->program)
-    if (nd.op == PQG_FILTER_CONTAINS) contained[(size_t)nd.left] = 1;
-  for (uint32_t i = 0; i < h.n_nodes; i++) {
-    const pqg_filter_node& nd = f->program[i];
-    pqg::FilterDevNode d{};
-    d.op = (uint8_t)nd.op;
-    d.flags = (uint8_t)(nd.flags | dev_flags[i] | (contained[i] ? pqg::FILTER_DEV_CONTAINED : 0u));
-    if (is_leaf(nd.op)) {
-      const pqg_filter_column_type& ct = f->columns[(size_t)nd.column];
-      d.type = (uint8_t)ct.physical_type;
-      d.slot = (uint8_t)(std::find(f->slot_column.begin(), f->slot_column.end(), nd.column) - f->slot_column.begin());
-      d.n_lit = (uint16_t)nd.n_literals;
-      d.lit_begin = img_begin[i];
-      d.width = ct.physical_type == PQG_INT96 ? 12u : ct.physical_type == PQG_FIXED_LEN_BYTE_ARRAY ? (uint32_t)ct.type_length : 0u;
-    } else {
-      d.left = (uint8_t)nd.left;
-      d.right = (uint8_t)(nd.right < 0 ? 0 : nd.right);
-    }
-    memcpy(img + sizeof(h) + i * sizeof(d), &d, sizeof(d));
-  }
-  if (h.n_cells) memcpy(img + h.cells_off, img_cells.data(), 8u * h.n_cells);
-  if (h.n_bytes) memcpy(img + h.bytes_off, lb, h.n_bytes);
-  memcpy(img, &h, sizeof(h));
+  build_image(f, false, &f->image);
+  build_image(f, true, &f->rg_image);
   *out = f;
   if (st) fail(st, PQG_OK, -1, "");
   return PQG_OK;

@@ -285,6 +285,30 @@ class FilterDictionary(C.Structure):
 assert C.sizeof(FilterDictionary) == 24
 
 
+# row-group dictionary filter (pqg_filter_row_groups)
+RG_MISSING, RG_NO_DICTIONARY, RG_NON_DICT_PAGES, RG_MAY_CONTAIN_NULL = 1, 2, 4, 8  # pqg_rowgroup_column.flags
+RG_TILE_ENTRIES = 1024  # PQG_RG_TILE_ENTRIES: dictionary entries of one work item
+
+
+class RowGroupColumn(C.Structure):
+    """pqg_rowgroup_column (32 bytes): the dictionary of one column chunk of one row group and what the host
+    knows of the chunk."""
+    _fields_ = [("dict", FilterDictionary), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RowGroupResult(C.Structure):
+    """pqg_rowgroup_result (16 bytes, device-resident)."""
+    _fields_ = [("n_kept", C.c_uint64), ("error", C.c_int32), ("error_group", C.c_int32)]
+
+
+class PageEncodingStat(C.Structure):
+    """pqg_page_encoding_stat (12 bytes): one entry of ColumnMetaData.encoding_stats."""
+    _fields_ = [("page_type", C.c_int32), ("encoding", C.c_int32), ("count", C.c_int32)]
+
+
+assert C.sizeof(RowGroupColumn) == 32 and C.sizeof(RowGroupResult) == 16 and C.sizeof(PageEncodingStat) == 12
+
+
 class FilterRecordColumn(C.Structure):
     """pqg_filter_record_column (64 bytes): a pqg_filter_column plus the column's repetition levels."""
     _fields_ = [("col", FilterColumn), ("max_rep", C.c_int32), ("reserved", C.c_int32), ("rep_levels", C.c_void_p),

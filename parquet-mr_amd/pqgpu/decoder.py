@@ -509,6 +509,53 @@ class Decoder:
         col.n_values = int(desc.values_written)
         return col
 
+    def decode_dictionaries(self, dbatch, column_indices):
+        """decode_dictionary for many columns of `dbatch` in one call (pqg_decode_dictionaries): a list of
+        required DeviceColumns, one per entry of `column_indices`, whatever their number in one plan. With the
+        dictionary pages of every row group of a file in one batch, this is what Decoder.filter_row_groups
+        reads. An error names the dictionary (its position in `column_indices`). There is no regrow-and-retry
+        here: a BYTE_ARRAY dictionary gets dict_size + 64 bytes, and the values of a PLAIN page are its bytes
+        less a 4-byte length each, so the buffer cannot turn out short (decode_dictionary's retry covers
+        buffers a caller sized by an estimate, which this call never makes)."""
+        idx = [int(i) for i in column_indices]
+        cols = []
+        for i in idx:
+            cd = dbatch.batch.columns[i]
+            t, tl, n = cd["physical_type"], cd["type_length"], int(cd["dict_num_values"])
+            binary = None
+            if t == abi.BYTE_ARRAY:
+                vals = torch.empty(max((n + 1) * 8, 16), dtype=torch.uint8, device=self.device)
+                binary = torch.empty(int(cd["dict_size"]) + 64, dtype=torch.uint8, device=self.device)
+            else:
+                vals = torch.empty(max(n * abi.elem_width(t, tl), 16), dtype=torch.uint8, device=self.device)
+            if self.poison is not None:
+                vals.fill_(self.poison)
+            cols.append(DeviceColumn(t, vals, None, None, tl, binary))
+        if not idx:
+            return cols
+        L = native.lib()
+        descs = (abi.ColumnDesc * len(idx))()
+        for k, (i, col) in enumerate(zip(idx, cols)):
+            desc, cd = descs[k], dbatch.batch.columns[i]
+            for f, v in cd.items():
+                setattr(desc, f, v)
+            desc.flags = 0
+            desc.values = col.values.data_ptr()
+            desc.values_capacity = int(cd["dict_num_values"]) + (1 if col.physical_type == abi.BYTE_ARRAY else 0)
+            if col.binary_data is not None:
+                desc.binary_data = col.binary_data.data_ptr()
+                desc.binary_capacity = col.binary_data.numel()
+        st = abi.Status()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        rc = L.pqg_decode_dictionaries(self.ctx, dbatch.bytes.data_ptr(), dbatch.n_bytes, C.addressof(descs), len(idx),
+                                       C.byref(st))
+        if rc == abi.OK:
+            rc = L.pqg_sync(self.ctx, C.byref(st))
+        native.check(rc, st, "pqg_decode_dictionaries")
+        for k, col in enumerate(cols):
+            col.n_values = int(descs[k].values_written)
+        return cols
+
     def _decode_once(self, dbatch, cols, page_counts):
         batch = dbatch.batch
         self.stream.wait_stream(torch.cuda.current_stream(self.device))  # uploads / allocations first
@@ -759,6 +806,59 @@ class Decoder:
         native.check(rc, what="pqg_filter_run_records")
         sel = F.Selection(self, n_rows, words[:n_words], ids, result, capacity)
         sel._keep = (flt, cols, [getattr(c, "dictionary", None) for c in cols])
+        return sel
+
+    def filter_row_groups(self, pred, row_groups, columns=None, capacity=None, out=None):
+        """DictionaryFilter.canDrop for every row group in one call (pqg_filter_row_groups): which row groups
+        can hold no record that satisfies `pred` (the pqgpu.filter DSL, or a created filter.Filter), judged
+        from their dictionaries alone, before any data page is uploaded. row_groups: one list of
+        filter.RowGroupColumn per row group, one entry per column of the schema. The columns' types come from
+        `columns` (types or objects with .physical_type) or, without it, from the RowGroupColumns. Asynchronous
+        on the decoder's stream; returns a filter.RowGroupSelection whose `drop` / `kept` / `count` wait for it.
+        capacity: kept ids to write (default: every row group). out: (bitmap int64 tensor, kept id int64 tensor,
+        16-byte uint8 result tensor) to write into instead of fresh tensors."""
+        from . import filter as F
+        n = len(row_groups)
+        n_cols = len(row_groups[0]) if n else (len(columns) if columns is not None else 0)
+        if any(len(g) != n_cols for g in row_groups):
+            raise ValueError("every row group lists the same columns")
+        if isinstance(pred, F.Filter):
+            flt = pred
+        else:
+            if columns is None:
+                columns = []
+                for c in range(n_cols):
+                    typed = next((g[c] for g in row_groups if g[c].physical_type is not None), None)
+                    if typed is None:
+                        raise ValueError(f"column {c}: no row group names its type (RowGroupColumn(physical_type=...))")
+                    columns.append(F.ColumnType(typed.physical_type, typed.type_length))
+            flt = F.Filter(pred, columns)
+        if flt.n_cols != n_cols and n:
+            raise native.PqgError(abi.ERR_INVALID_ARG, what="pqg_filter_row_groups: not the filter's column count")
+        arr = (abi.RowGroupColumn * max(1, n * n_cols))()
+        for g, group in enumerate(row_groups):
+            for c, rc in enumerate(group):
+                a = arr[g * n_cols + c]
+                d = rc.dictionary
+                if d is not None:
+                    a.dict.values = d.values.data_ptr()
+                    a.dict.binary_data = d.binary_data.data_ptr() if d.binary_data is not None else None
+                    a.dict.n_entries = d.n_values
+                a.flags = rc.flags
+        n_words = (n + 63) // 64
+        capacity = n if capacity is None else int(capacity)
+        if out is not None:
+            words, ids, result = out
+        else:
+            words = torch.empty(max(n_words, 1), dtype=torch.int64, device=self.device)
+            ids = torch.empty(max(capacity, 1), dtype=torch.int64, device=self.device)
+            result = torch.empty(16, dtype=torch.uint8, device=self.device)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))  # allocations / fills first
+        rc = native.lib().pqg_filter_row_groups(self.ctx, flt.handle, C.addressof(arr), flt.n_cols, n, words.data_ptr(),
+                                                ids.data_ptr(), capacity, result.data_ptr())
+        native.check(rc, what="pqg_filter_row_groups")
+        sel = F.RowGroupSelection(self, n, words[:n_words], ids, result, capacity)
+        sel._keep = (flt, row_groups)
         return sel
 
     # -- row selection ----------------------------------------------------------------

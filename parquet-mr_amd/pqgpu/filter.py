@@ -315,3 +315,77 @@ class Selection:
         if self._ids is None:
             return None
         return self._ids[:min(self._sync(), self._capacity)]
+
+
+class ColumnType:
+    """A column known by its type alone: what Filter needs of a column (Decoder.filter_row_groups has no
+    decoded columns to take the types from)."""
+
+    def __init__(self, physical_type, type_length=0):
+        self.physical_type = int(physical_type)
+        self.type_length = int(type_length or 0)
+
+
+class RowGroupColumn:
+    """What a reader knows of one column chunk of one row group before it reads a page (Decoder.filter_row_groups):
+    `dictionary`, the chunk's decoded dictionary page (the DeviceColumn of Decoder.decode_dictionary /
+    decode_dictionaries; None: no dictionary page was read); missing: the file has no such column;
+    non_dictionary_pages: framing.has_non_dictionary_pages of the chunk's metadata; may_contain_null: the chunk's
+    statistics are absent, leave num_nulls unset or count a null. physical_type / type_length name the column's type
+    where no row group carries a dictionary for it (they default to the dictionary's)."""
+
+    def __init__(self, dictionary=None, missing=False, non_dictionary_pages=False, may_contain_null=True,
+                 physical_type=None, type_length=0):
+        self.dictionary = dictionary
+        self.missing = bool(missing)
+        self.non_dictionary_pages = bool(non_dictionary_pages)
+        self.may_contain_null = bool(may_contain_null)
+        self.physical_type = dictionary.physical_type if physical_type is None and dictionary is not None else physical_type
+        self.type_length = int(getattr(dictionary, "type_length", 0) or 0) if dictionary is not None else int(type_length)
+
+    @property
+    def flags(self):
+        return ((abi.RG_MISSING if self.missing else 0) | (abi.RG_NO_DICTIONARY if self.dictionary is None else 0) |
+                (abi.RG_NON_DICT_PAGES if self.non_dictionary_pages else 0) |
+                (abi.RG_MAY_CONTAIN_NULL if self.may_contain_null else 0))
+
+
+class RowGroupSelection:
+    """Outcome of Decoder.filter_row_groups: `drop` (torch bool, one per row group: the group cannot match),
+    `kept` (torch int64, the other groups ascending, at most the capacity asked for), `count` (how many are kept) and `bitmap` (the int64 view of
+    the uint64 words: group g is bit g & 63 of word g >> 6). Reading any of the first three waits for the stream."""
+
+    def __init__(self, decoder, n_row_groups, words, ids, result, capacity):
+        self._decoder = decoder
+        self._capacity = capacity
+        self.n_row_groups = n_row_groups
+        self.bitmap = words
+        self._ids = ids
+        self._result = result
+        self._host = None
+
+    def _sync(self):
+        if self._host is None:
+            self._decoder.stream.synchronize()
+            r = self._result.cpu().numpy()
+            err, group = (int(x) for x in r[8:16].view(np.int32))
+            if err != abi.OK:
+                raise native.PqgError(err, what=f"pqg_filter_row_groups: row group {group}")
+            self._host = int(r[:8].view(np.uint64)[0])
+        return self._host
+
+    @property
+    def count(self):
+        return self._sync()
+
+    @property
+    def kept(self):
+        return self._ids[:min(self._sync(), self._capacity)]
+
+    @property
+    def drop(self):
+        import torch
+        self._sync()
+        shifts = torch.arange(64, dtype=torch.int64, device=self.bitmap.device)
+        bits = (self.bitmap.unsqueeze(1) >> shifts) & 1
+        return bits.reshape(-1)[:self.n_row_groups].to(torch.bool)

@@ -234,3 +234,21 @@ def frame_chunk_native(chunk_bytes, value_count=-1, verify_crc=True):
             cap = n.value
             continue
         return rc, st, [hdrs[i] for i in range(min(n.value, cap))]
+
+
+def has_non_dictionary_pages(encoding_stats, encodings):
+    """DictionaryFilter.hasNonDictionaryPages over a chunk's ColumnMetaData (pqg_chunk_has_non_dictionary_pages):
+    encoding_stats is None (the chunk has none) or a list of (page_type, encoding, count); encodings is the
+    chunk's encodings list. True: a data page may not be dictionary-encoded, so the dictionary cannot drop the
+    row group (filter.RowGroupColumn(non_dictionary_pages=True))."""
+    import numpy as np
+
+    from . import native
+    enc = np.asarray(list(encodings), dtype=np.int32)
+    if encoding_stats is None:
+        stats, n = None, -1
+    else:
+        arr = np.asarray([tuple(int(x) for x in s) for s in encoding_stats], dtype=np.int32).reshape(-1, 3)
+        arr = np.ascontiguousarray(arr)
+        stats, n = (arr.ctypes.data if arr.size else None), arr.shape[0]
+    return bool(native.lib().pqg_chunk_has_non_dictionary_pages(stats, n, enc.ctypes.data if enc.size else None, enc.size))

@@ -44,6 +44,8 @@ EXPORTS = [
     "pqg_take_records",
     # page checksums on the device, and their host helpers
     "pqg_crc32_pages", "pqg_crc32_sync", "pqg_crc32_combine", "pqg_crc_jobs_from_headers",
+    # row-group dictionary filter (DictionaryFilter.canDrop for every row group of a file)
+    "pqg_filter_row_groups", "pqg_chunk_has_non_dictionary_pages", "pqg_decode_dictionaries",
 ]
 
 
@@ -127,6 +129,9 @@ def lib():
         L.pqg_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, u64]
         L.pqg_crc32_combine.restype = C.c_uint32
         L.pqg_crc_jobs_from_headers.argtypes = [vp, i32, u64, vp, vp, i32, C.POINTER(i32), C.POINTER(abi.Status)]
+        L.pqg_decode_dictionaries.argtypes = [vp, vp, u64, vp, i32, C.POINTER(abi.Status)]
+        L.pqg_filter_row_groups.argtypes = [vp, vp, vp, i32, u64, vp, vp, u64, vp]
+        L.pqg_chunk_has_non_dictionary_pages.argtypes = [vp, i32, vp, i32]
         L.pqg_error_name.argtypes = [i32]
         L.pqg_error_name.restype = C.c_char_p
         if L.pqg_abi_version() != abi.ABI_VERSION:
