@@ -135,14 +135,21 @@ def window_offsets(body, n):
 WORDS = [b"", b"a", b"bc", b"def", b"ghijklmnopqrstuvwxyz"]
 
 
-def chunk(pages, ptype=abi.INT64):
-    """A dictionary column of CARD entries whose pages are [(body, value count)]."""
-    if ptype == abi.BYTE_ARRAY:
-        vals = [WORDS[i % CARD] for i in range(8 * len(pages))]
+def chunk(pages, ptype=abi.INT64, card=CARD, dictionary=None):
+    """A dictionary column whose pages are [(body, value count)]: `card` entries 0 .. card - 1 (words
+    for BYTE_ARRAY), or the entries of `dictionary` (INT32 / INT64) in the order given."""
+    rows = 8  # values per page of the column that make() writes (replaced below)
+    if dictionary is not None:
+        card = len(dictionary)
+        rows = max(8, -(-card // len(pages)))
+        vals = np.resize(np.asarray(dictionary, dtype=abi.numpy_dtype(ptype)), rows * len(pages))
+        assert len(set(vals[:card].tolist())) == card  # distinct, cycled: entry i gets id i
+    elif ptype == abi.BYTE_ARRAY:
+        vals = [WORDS[i % card] for i in range(rows * len(pages))]
     else:
-        vals = (np.arange(8 * len(pages)) % CARD).astype(abi.numpy_dtype(ptype))
-    ch = make(ptype, vals, abi.RLE_DICTIONARY, page_rows=8)
-    assert len(ch.pages) == len(pages) and ch.dict_num_values == CARD
+        vals = (np.arange(rows * len(pages)) % card).astype(abi.numpy_dtype(ptype))
+    ch = make(ptype, vals, abi.RLE_DICTIONARY, page_rows=rows)
+    assert len(ch.pages) == len(pages) and ch.dict_num_values == card
     for pg, (body, n) in zip(ch.pages, pages):
         pg.body, pg.num_values, pg.num_rows = body, n, n
     ch.values = None
