@@ -47,13 +47,6 @@ __device__ __forceinline__ void asm_load16(const uint8_t* __restrict__ a, uint64
   }
 }
 
-__device__ __forceinline__ uint32_t bt_at(const uint32_t (&bt)[ASM_MAX_DEPTHS], uint32_t q) {
-  uint32_t v = 0;
-#pragma unroll
-  for (uint32_t d = 0; d < ASM_MAX_DEPTHS; d++) v = d == q ? bt[d] : v;
-  return v;
-}
-
 __device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[4], uint32_t j) { return (w[j >> 2] >> (8 * (j & 3))) & 0xFFu; }
 
 __global__ __launch_bounds__(256) void k_asm_count(const uint8_t* __restrict__ def, const uint8_t* __restrict__ rep,

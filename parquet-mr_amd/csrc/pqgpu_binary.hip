@@ -2049,7 +2049,7 @@ struct BpGuess {
 // The chain from pos through tile [B, B + BW_WIN): accepted value starts to L.acc[0, n). With
 // list0 < BW_CAP the candidate list of the whole tile is already in LDS (bp_guess) and pos is its
 // candidate list0 (total0 candidates, listed up to eff0).
-template <bool FAST, class LdsT>
+template <class LdsT>
 __device__ BpWalk bp_walk(LdsT& L, const BwBytes& cur, rsrc_t rs, uint32_t B, uint32_t pos, uint32_t end,
                           uint32_t list0 = 0xFFFFFFFFu, uint32_t total0 = 0, uint32_t eff0 = 0, bool list_fast = false) {
   BinWalkLds& W = L.u.w;
@@ -2058,7 +2058,7 @@ __device__ BpWalk bp_walk(LdsT& L, const BwBytes& cur, rsrc_t rs, uint32_t B, ui
   int code = 0;
   const uint32_t tend = B + BW_WIN;
   bool listed = list0 < BW_CAP;
-  bool fast = listed ? list_fast : FAST;  // short lengths first; every length once a value start is missing
+  bool fast = listed ? list_fast : true;  // short lengths first; every length once a value start is missing
   while (true) {
     pos = uni(pos);
     n = uni(n);
@@ -2487,8 +2487,8 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6))) v
 #endif
   BpWalk r{entry, 0, 0};
   if (entry != 0xFFFFFFFFu) {
-    r = first ? bp_walk<true>(L, cur, rs, B, entry, end)
-              : bp_walk<true>(L, cur, rs, B, entry, end, gs.index, gs.total, gs.eff_end, gs.fast);
+    r = first ? bp_walk(L, cur, rs, B, entry, end)
+              : bp_walk(L, cur, rs, B, entry, end, gs.index, gs.total, gs.eff_end, gs.fast);
     if (!first && lane == 0)  // speculative: count, guessed entry, exit, stop
       sst(aggw + t, E | ((uint64_t)r.n << 46) | ((uint64_t)(entry - B) << 35) | ((uint64_t)(r.code ? 1u : 0u) << 34) |
                         (uint64_t)r.pos);
@@ -2537,7 +2537,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(6))) v
 #endif
             if (ex0 != entry) {                    // misspeculated (or no guess): walk from there
               entry = ex0;
-              r = ex0 >= B + BW_WIN ? BpWalk{ex0, 0, 0} : bp_walk<true>(L, cur, rs, B, ex0, end);
+              r = ex0 >= B + BW_WIN ? BpWalk{ex0, 0, 0} : bp_walk(L, cur, rs, B, ex0, end);
             }
           }
           break;
@@ -2643,7 +2643,7 @@ __global__ __launch_bounds__(64 * WPB) __attribute__((amdgpu_waves_per_eu(5))) v
     pos = uni(pos);
     before = uni(before);
     B = uni(B);
-    const BpWalk r = bp_walk<true>(L, cur, rs, B, pos, end);
+    const BpWalk r = bp_walk(L, cur, rs, B, pos, end);
     if (r.code && before + r.n < N && lane == 0) report(err, err_count, page, 2, before + r.n, r.code);
     bool last = r.code != 0;
     if (before + r.n >= N) {  // the page's last value is here: it must end at the section end
@@ -2786,8 +2786,8 @@ __global__ __launch_bounds__(64 * WPB) void k_dent_walk(const uint8_t* __restric
   const BpGuess gs = s == 0 ? BpGuess{0u, 0xFFFFFFFFu, 0, 0, false} : bp_guess(L, cur, rs, B, end);
   BpWalk r{gs.pos, 0, 0};
   if (gs.pos != 0xFFFFFFFFu)
-    r = s == 0 ? bp_walk<true>(L, cur, rs, B, 0u, end)
-               : bp_walk<true>(L, cur, rs, B, gs.pos, end, gs.index, gs.total, gs.eff_end, gs.fast);
+    r = s == 0 ? bp_walk(L, cur, rs, B, 0u, end)
+               : bp_walk(L, cur, rs, B, gs.pos, end, gs.index, gs.total, gs.eff_end, gs.fast);
   for (uint32_t k = lane; k < r.n; k += WAVE) gst(scr + (uint64_t)t * BW_CAP + k, L.acc[k]);
   if (lane == 0) {
     gst(rec + 2u * t, (uint64_t)gs.pos | ((uint64_t)r.pos << 32));
@@ -2854,7 +2854,7 @@ __global__ __launch_bounds__(64) void k_dent_resolve(const uint8_t* __restrict__
     uint32_t cd_code = uni(rdl((uint32_t)(r1 >> 32), j));
     if (s != 0 && guess != entry) {  // misspeculated (or no guess): this wave walks the tile from its true entry
       const BwBytes cur = bw_load(rs, B);
-      const BpWalk rr = bp_walk<true>(L, cur, rs, B, entry, end);
+      const BpWalk rr = bp_walk(L, cur, rs, B, entry, end);
       for (uint32_t k = lane; k < rr.n; k += WAVE) gst(scr + (uint64_t)t * BW_CAP + k, L.acc[k]);
       ex = rr.pos;
       cnt = rr.n;

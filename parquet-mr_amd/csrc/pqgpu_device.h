@@ -1,7 +1,7 @@
 // pqgpu_device.h — device helpers shared by the CDNA4 (gfx950) kernels of the decoder:
 // wave/lane ids, buffer resources with hardware range checks, global/system-scope
-// stores and loads, error reporting, the register byte window and the varint readers
-// (BytesUtils.readUnsignedVarInt / readUnsignedVarLong / readZigZagVarLong).
+// stores and loads, the wave scans, error reporting, the register byte window and
+// BytesUtils.readZigZagVarLong.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,6 +16,22 @@ constexpr int WAVE = 64;
 // waves resident), so pages are packed 4 to a workgroup.
 constexpr int WPB = 4;
 
+// Tiles (64 lanes x 16 bytes) per output chunk of the dictionary expansion and of the
+// dictionary-direct string kernels.
+constexpr uint32_t CH_TILES = DICT_CHUNK_TILES;
+
+// Value type of a W-byte column (dictionary entries, DELTA_BINARY_PACKED values): W = 4 or 8.
+template <int W>
+struct DictVal;
+template <>
+struct DictVal<8> {
+  typedef uint64_t T;
+};
+template <>
+struct DictVal<4> {
+  typedef uint32_t T;
+};
+
 __device__ __forceinline__ uint32_t wave_id() {
   return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
@@ -25,9 +41,10 @@ __device__ __forceinline__ int wave_page(const int32_t* list, int n_list) {
   return i < n_list ? list[i] : -1;
 }
 #ifdef PQG_DIAG
-// Diagnostic build only (libpqgpu_diag.so, tools/diag_timeline.py): per-wave
-// stamps. Never compiled into the product library.
-static __device__ uint64_t* pqg_diag_buf;
+// Diagnostic build only (tools/build_variant.sh -DPQG_DIAG, tools/diag_*.py): per-wave stamps. Never
+// compiled into the product library. The variables are static: every translation unit has its own
+// copy, set by a pqg::diag_* function of the file that reads it (the exported pqg_diag_*_set of
+// pqgpu_dict.hip call them).
 static __device__ uint64_t* pqg_diag_wrt;  // per page: s_memrealtime at walk start / publish
 static __device__ uint64_t* pqg_diag_xrt;  // per chunk: start, flag seen, end, (page | cu << 32)
 static __device__ uint64_t* pqg_diag_wph;  // per page: list-walk cycles (predecode, chain, emit), windows, batches, runs
@@ -102,6 +119,19 @@ __device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t x) {
   return x;
 }
 
+// Inclusive prefix sum over the wave (u32) with DPP row shifts / broadcasts; all 64 lanes active.
+__device__ __forceinline__ uint32_t wave_incl_scan_u32_dpp(uint32_t x) {
+#define PQG_DPP_ADD(ctrl, rmask) x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, ctrl, rmask, 0xf, true);
+  PQG_DPP_ADD(0x111, 0xf)  // row_shr:1
+  PQG_DPP_ADD(0x112, 0xf)  // row_shr:2
+  PQG_DPP_ADD(0x114, 0xf)  // row_shr:4
+  PQG_DPP_ADD(0x118, 0xf)  // row_shr:8
+  PQG_DPP_ADD(0x142, 0xa)  // row_bcast:15 -> rows 1, 3
+  PQG_DPP_ADD(0x143, 0xc)  // row_bcast:31 -> rows 2, 3
+#undef PQG_DPP_ADD
+  return x;
+}
+
 // Exclusive scan in place of a[0, n) by one 256-thread workgroup, PER elements per thread per round;
 // returns the total (in every thread). Call with the whole workgroup.
 template <int PER>
@@ -133,15 +163,6 @@ __device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t* __restrict__ a
     __syncthreads();
   }
   return carry;
-}
-
-// Mask of bytes [jb, je) (clamped) within dword i of a 16-byte block.
-__device__ __forceinline__ uint32_t block_byte_mask(int32_t jb, int32_t je, int32_t i) {
-  const int32_t lo = jb - 4 * i < 0 ? 0 : (jb - 4 * i > 4 ? 4 : jb - 4 * i);
-  const int32_t hi = je - 4 * i < 0 ? 0 : (je - 4 * i > 4 ? 4 : je - 4 * i);
-  const uint32_t mh = hi >= 4 ? 0xFFFFFFFFu : (1u << (8 * hi)) - 1u;
-  const uint32_t ml = lo >= 4 ? 0xFFFFFFFFu : (1u << (8 * lo)) - 1u;
-  return mh & ~ml;
 }
 
 // Minimum over the wave (u32), in every lane.
@@ -321,51 +342,7 @@ struct Window {
     if (sh) x = (x >> sh) | ((uint64_t)dword(i + 2) << (64u - sh));
     return x;
   }
-  __device__ __forceinline__ uint32_t byte(uint32_t p) {
-    ensure(p);
-    uint32_t k = p - B;
-    return (dword(k >> 2) >> ((k & 3u) * 8u)) & 0xFFu;
-  }
 };
-
-// readUnsignedVarInt (BytesUtils.java:202-211) at p. Sets len; Java int shift masking.
-// `lim` = bytes readable before the section end; a varint not terminated within
-// them gets len = lim + 1 (the caller's EOF check fails it, as read() would).
-__device__ __forceinline__ uint32_t read_uvarint(Window& w, uint32_t p, uint32_t lim, uint32_t& len) {
-  uint64_t x = w.read8(p);
-  uint32_t b0 = (uint32_t)x & 0xFFu;
-  if (!(b0 & 0x80u)) { len = 1; return b0; }
-  uint32_t b1 = (uint32_t)(x >> 8) & 0xFFu;
-  if (!(b1 & 0x80u)) { len = 2; return (b0 & 0x7Fu) | (b1 << 7); }
-  uint32_t value = 0, i = 0, k = 0, b;
-  for (;;) {
-    b = (k < 8u) ? (uint32_t)(x >> (8u * k)) & 0xFFu : w.byte(p + k);
-    if (!(b & 0x80u)) break;
-    value |= (b & 0x7Fu) << (i & 31u);
-    i += 7;
-    k++;
-    if (k >= lim) break;
-  }
-  len = k + 1;
-  return value | (b << (i & 31u));
-}
-
-// readUnsignedVarLong (BytesUtils.java:260-269), Java long shift masking.
-__device__ __forceinline__ uint64_t read_uvarlong(Window& w, uint32_t p, uint32_t lim, uint32_t& len) {
-  uint64_t value = 0;
-  uint32_t i = 0, k = 0, b;
-  uint64_t x = w.read8(p);
-  for (;;) {
-    b = (k < 8u) ? (uint32_t)(x >> (8u * k)) & 0xFFu : w.byte(p + k);
-    if (!(b & 0x80u)) break;
-    value |= (uint64_t)(b & 0x7Fu) << (i & 63u);
-    i += 7;
-    k++;
-    if (k >= lim) break;
-  }
-  len = k + 1;
-  return value | ((uint64_t)b << (i & 63u));
-}
 
 // readZigZagVarLong (BytesUtils.java:254-258)
 __device__ __forceinline__ int64_t zigzag64(uint64_t r) {

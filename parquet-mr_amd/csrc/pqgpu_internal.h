@@ -19,6 +19,13 @@ struct ErrCount {
   uint32_t epoch;
 };
 
+#ifdef PQG_DIAG
+// Diagnostic build: the pqg_diag_* variables (pqgpu_device.h) are static, one copy per file; each file that
+// reads one sets its own, and the exported pqg_diag_*_set (pqgpu_dict.hip) call these. 0, or 3 on failure.
+int diag_nostore_dict_strings(int v), diag_nostore_plain(int v), diag_nostore_kernels(int v);
+int diag_wph_kernels(void* p);
+#endif
+
 hipError_t launch_dict(int width, hipStream_t st, const uint8_t* bytes, uint64_t n_bytes, PageWork* work,
                        const ColumnDev* cols, const int32_t* list, int n, uint64_t* rec, uint32_t* chunk_run,
                        const uint64_t* chunks, uint32_t n_chunks, uint64_t* pstat, uint32_t* flags, uint32_t epoch,
@@ -54,6 +61,17 @@ hipError_t launch_dict_dd(hipStream_t st, const uint8_t* bytes, uint64_t n_bytes
                           uint32_t epoch, bool fused, uint64_t* err, ErrCount err_count, uint64_t* sums,
                           const int32_t* dd_cols, const int32_t* dd_start, int n_dd_cols, uint32_t dd_region,
                           bool global, hipEvent_t entries_ready = nullptr);
+// pqgpu_dict_strings.hip: what launch_dict_dd runs after the ids and sums (`sums` holds the chunks' byte
+// sums, or nothing yet when `global`): the wait for entries_ready, k_dd_gsums (global), k_dd_bases, then
+// k_dd_str or k_dd_gstr
+hipError_t launch_dd_strings(hipStream_t st, const uint8_t* bytes, uint64_t n_bytes, PageWork* work,
+                             const ColumnDev* cols, const uint64_t* chunks, uint32_t n_chunks, const uint64_t* pstat,
+                             uint64_t* err, ErrCount err_count, uint64_t* sums, const int32_t* dd_cols,
+                             const int32_t* dd_start, int n_dd_cols, uint32_t dd_region, bool global,
+                             hipEvent_t entries_ready);
+// BOOLEAN values with encoding RLE (k_rle_bool runs the level decoder); launch_plain's kind 2
+hipError_t launch_rle_bool(hipStream_t st, const uint8_t* bytes, uint64_t n_bytes, PageWork* work,
+                           const ColumnDev* cols, const int32_t* list, int n, uint64_t* err, ErrCount err_count);
 // DELTA_LENGTH_BYTE_ARRAY lengths (k_delta into blen, records PageWork::aux)
 hipError_t launch_dlba_lengths(hipStream_t st, const uint8_t* bytes, uint64_t n_bytes, PageWork* work,
                                const ColumnDev* cols, const int32_t* list, int n, uint64_t* err, ErrCount err_count);

@@ -79,7 +79,7 @@ static_assert(sizeof(PageWork) == 104, "PageWork layout");
 
 enum BinKind : uint32_t { BIN_PLAIN = 0, BIN_DLBA = 1, BIN_DICT = 2, BIN_DBA = 3 };
 
-// Output chunk of k_dict_expand: CH_TILES x 64 lanes x 16 bytes.
+// Output chunk of the dictionary expansion (k_dict_tiles / dict_tiles_body): DICT_CHUNK_TILES x 64 lanes x 16 bytes.
 constexpr uint32_t DICT_CHUNK_TILES = 16;
 inline uint32_t dict_chunk_values(int elem_width) { return DICT_CHUNK_TILES * 64u * (16u / (uint32_t)elem_width); }
 // output chunks of a dictionary page of n slots (slots shifted by up to 16 / width - 1 for 16-B alignment)
@@ -103,6 +103,7 @@ constexpr uint32_t SCAN_BLOCK = 4096;   // values per offset-scan block
 // str_dict dictionary, 1,000 entries of 4-32 bytes in 22 KB, then took the per-value path: 0.667 ms, now
 // 0.347 ms, profiles/r05/dd32k; k_dd_str's LDS at 32 KiB + the entry table: 4 workgroups per CU)
 constexpr uint32_t DD_DICT_MAX = 32768;
+constexpr uint32_t DD_ENT_MAX = 2048;  // entries of a dictionary page of at most DD_DICT_MAX bytes (4-byte lengths)
 // BYTE_ARRAY dictionary pages of at least DENT_MIN bytes: entries walked per 2 KiB tile in parallel
 // (k_dent_walk, k_dent_resolve, k_dent_scatter) instead of one wave per page. tiles: column | tile << 32
 // (in column order; dictionary dcols[i]'s tiles are [dstart[i], dstart[i + 1])); scratch per tile: rec

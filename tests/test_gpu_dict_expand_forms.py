@@ -1,4 +1,4 @@
-"""GPU parity of the dictionary expansion (dict_tiles_body in csrc/pqgpu_kernels.hip, run by
+"""GPU parity of the dictionary expansion (dict_tiles_body in csrc/pqgpu_dict.hip, run by
 k_dict_fused<W> / k_dict_tiles<W> and their IDS variants) on hand-built run shapes: the counterpart of
 test_gpu_dict_walk_forms.py, which puts *headers* on the walk's window edges; the pages here put *values*
 on the expansion's output seams.

@@ -1,4 +1,4 @@
-"""Recovery from the fused dictionary kernel's wait timeout (pqgpu_kernels.hip SPIN_TIMEOUT_TICKS).
+"""Recovery from the fused dictionary kernel's wait timeout (pqgpu_dict.hip SPIN_TIMEOUT_TICKS).
 
 The fused kernel's expansion workgroups wait for the walker workgroups of their pages; HIP does not
 promise that walkers are dispatched first. When a wait exceeds the timeout the launch reports

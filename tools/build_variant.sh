@@ -2,9 +2,10 @@
 # Diagnostic build of libpqgpu.so with extra defines (A/B experiments; loaded through PQGPU_LIB):
 #   bash tools/build_variant.sh abx/libnoval.so -DPQG_XT_NOVALUE
 set -euo pipefail
-OUT=$1; shift
+OUT=$(realpath -m "$1"); shift
+cd "$(dirname "$0")/.."  # the repository root: the paths below and __graft_entry__ are relative to it
 C=parquet-mr_amd/csrc
+# the source list of build() (__graft_entry__.SOURCES), so there is no second one to keep
+SRC=$(python3 -c 'import __graft_entry__ as g; print(" ".join("'$C'/" + f for f in g.SOURCES))')
 mkdir -p "$(dirname "$OUT")"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -shared "$@" -o "$OUT" \
-  $C/pqgpu_kernels.hip $C/pqgpu_binary.hip $C/pqgpu_assembly.hip $C/pqgpu_snappy.hip $C/pqgpu_zstd.hip $C/pqgpu_lz4.hip $C/pqgpu_gzip.hip \
-  $C/pqgpu_api.hip $C/pqgpu_framing.cpp $C/pqgpu_reader.cpp -Wl,--no-undefined
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -shared "$@" -o "$OUT" $SRC -Wl,--no-undefined

@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256) void k_stream(v2* out, u64 n16, u64 span16) {
 }
 
 // Persistent: workgroup g owns a contiguous region; its 4 waves take chunks of `chunk16`
-// round-robin (the k_dict_expand assignment).
+// round-robin (the assignment of the former persistent expansion kernel).
 template <bool NT>
 __global__ __launch_bounds__(256) void k_wg_chunks(v2* out, u64 n16, u64 chunk16, u64 per_wg) {
   const u64 lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
