@@ -43,7 +43,9 @@
  * FIXED_LEN_BYTE_ARRAY columns and the three binary comparators (pqg_filter_binary_order,
  * pqg_filter_column_type, pqg_filter_create_typed); page checksums on the device (pqg_crc_job,
  * pqg_crc32_pages, pqg_crc32_sync, PQG_DISPATCH_CRC_TILE_BYTES) with the host helpers pqg_crc32_combine
- * and pqg_crc_jobs_from_headers.
+ * and pqg_crc_jobs_from_headers; encrypted pages on the device (pqg_decrypt_job, pqg_aes_key,
+ * pqg_decrypt_pages, pqg_decrypt_sync, pqg_copy_range, pqg_copy_ranges, PQG_ERR_TAG,
+ * PQG_DISPATCH_AES_TILE_BYTES) with the host helper pqg_module_aad.
  * ABI 5: record-level filter2 predicates over decoded columns (pqg_filter_create /
  * pqg_filter_program / pqg_filter_destroy on the host, pqg_filter_run on the device).
  * ABI 4: pqg_page_desc carries the V2 header's num_nulls
@@ -124,8 +126,9 @@ enum pqg_error {
   PQG_ERR_CORRUPT = 18,         /* section lengths inconsistent with the page (negative/oversized length prefix) */
   PQG_ERR_NO_DICTIONARY = 19,   /* "could not read page ... as the dictionary was missing" (ColumnReaderBase.java:709-712) */
   PQG_ERR_DICT_ENCODING = 20,   /* "Dictionary data encoding type not supported" (PlainValuesDictionary.java:49-52) */
-  PQG_ERR_CRC = 21              /* ParquetDecodingException "could not verify page integrity, CRC checksum
+  PQG_ERR_CRC = 21,             /* ParquetDecodingException "could not verify page integrity, CRC checksum
                                    verification failed" (ParquetFileReader.java:1805-1813) */
+  PQG_ERR_TAG = 22              /* TagVerificationException "GCM tag check failed" (AesGcmDecryptor.java:71-72) */
 };
 
 /*
@@ -267,6 +270,8 @@ void* pqg_ctx_stream(pqg_ctx* ctx);
  *                                fallback); applies to later pqg_zstd_decompress calls
  *   PQG_DISPATCH_CRC_TILE_BYTES  pqg_crc32_pages: bytes of a range one wave checksums: 4096, 8192, 16384
  *                                or 32768 (default PQG_CRC_TILE_BYTES); applies to later calls
+ *   PQG_DISPATCH_AES_TILE_BYTES  pqg_decrypt_pages: ciphertext bytes of a module one wave decrypts: a power
+ *                                of two from 1024 to 32768 (default PQG_AES_TILE_BYTES); applies to later calls
  * Returns PQG_ERR_INVALID_ARG for an unknown key or value. Not thread-safe (like the ctx). */
 enum pqg_dispatch {
   PQG_DISPATCH_PLAIN_ONE_PASS = 1,
@@ -276,7 +281,8 @@ enum pqg_dispatch {
   PQG_DISPATCH_NULL_HINTS = 5,
   PQG_DISPATCH_TAKE_STAGED = 6,
   PQG_DISPATCH_ZSTD_PREPASS = 7,
-  PQG_DISPATCH_CRC_TILE_BYTES = 8
+  PQG_DISPATCH_CRC_TILE_BYTES = 8,
+  PQG_DISPATCH_AES_TILE_BYTES = 9
 };
 int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value);
 
@@ -1218,6 +1224,101 @@ uint32_t pqg_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
  * st->value_index = the count needed (as pqg_frame_chunk). */
 int pqg_crc_jobs_from_headers(const pqg_page_header* headers, int n_headers, uint64_t chunk_offset, pqg_crc_job* jobs,
                               int32_t* header_of_job, int capacity, int* n_jobs, pqg_status* st);
+
+/* ---- encrypted pages (an addition to ABI 6) ---------------------------------------------------------
+ * Parquet Modular Encryption: ColumnChunkPageReadStore decrypts a page between verifyCrc and the
+ * decompressor (ColumnChunkPageReadStore.java:140-175, 218-251, 321-322: blockDecryptor.decrypt(bytes,
+ * dataPageAAD)). pqg_decrypt_pages decrypts many modules of one device buffer into a second one, where
+ * the codec kernels or pqg_decode read the plaintext afterwards.
+ *
+ * A job is one module as BlockCipher.Encryptor wrote it:
+ *   PQG_DECRYPT_GCM  [4-byte LE length][12-byte nonce][ciphertext][16-byte tag]   (AesGcmDecryptor)
+ *   PQG_DECRYPT_CTR  [4-byte LE length][12-byte nonce][ciphertext]                (AesCtrDecryptor)
+ * (AesCipher.SIZE_LENGTH, NONCE_LENGTH, GCM_TAG_LENGTH). The plaintext has src_size - 32 bytes (GCM) or
+ * src_size - 16 (CTR). GCM: J0 = nonce || 00000001, the data counter starts at 2, the tag is checked over
+ * the AAD and the ciphertext. CTR: the IV is nonce || 00000001, the counter starts at 1, the AAD is
+ * ignored and nothing is verified. The value of the length field is skipped, not checked, as in the
+ * reference's decrypt(byte[], byte[]).
+ *
+ * AES-CTR is independent per 16-byte block and GHASH is a polynomial evaluation over GF(2^128): a module
+ * splits into tiles of PQG_AES_TILE_BYTES (one wave per tile: keystream, plaintext, the tile's GHASH
+ * partial), and a second launch folds the partials of a module through powers of H together with its
+ * AAD blocks, the zero padding and the length block, and compares with E_K(J0) ^ tag. No workgroup waits
+ * on another and there are no atomics. */
+#define PQG_AES_TILE_BYTES 16384    /* ciphertext bytes one wave decrypts; PQG_DISPATCH_AES_TILE_BYTES */
+#define PQG_DECRYPT_GCM 0           /* pqg_decrypt_job.mode: AES_GCM_V1 page modules, and all of AES_GCM_CTR_V1's
+                                       other modules */
+#define PQG_DECRYPT_CTR 1           /* pqg_decrypt_job.mode: the page modules of AES_GCM_CTR_V1 */
+#define PQG_MODULE_DATA_PAGE 2        /* ModuleCipherFactory.ModuleType.DataPage */
+#define PQG_MODULE_DICTIONARY_PAGE 3  /* ModuleCipherFactory.ModuleType.DictionaryPage */
+
+typedef struct pqg_decrypt_job {    /* sizeof == 40 */
+  uint64_t src_offset;  /* first byte of the module (its length field) in d_src, any alignment */
+  uint64_t dst_offset;  /* first byte of the plaintext in d_dst, any alignment */
+  uint32_t src_size;    /* bytes of the whole module */
+  uint32_t aad_offset;  /* the module's AAD in the host AAD blob (pqg_module_aad); ignored by CTR */
+  uint32_t aad_length;
+  int32_t mode;         /* PQG_DECRYPT_GCM / PQG_DECRYPT_CTR */
+  int32_t key;          /* index into `keys` */
+  uint32_t reserved;    /* 0 */
+} pqg_decrypt_job;
+
+typedef struct pqg_aes_key {        /* sizeof == 36 */
+  uint8_t bytes[32];
+  uint32_t size;        /* 16, 24 or 32 */
+} pqg_aes_key;
+
+/* d_dst[dst_offset, dst_offset + plaintext size) of job j <- the plaintext of the module at
+ * d_src[src_offset, src_offset + src_size); d_status[j] (device, n_jobs) <- PQG_OK, or PQG_ERR_TAG when a
+ * GCM module's tag does not verify (AesGcmDecryptor's TagVerificationException). The plaintext of a
+ * failed job is undefined, but no store leaves [dst_offset, dst_offset + plaintext size) of any job.
+ * Asynchronous on the ctx stream. `jobs`, `keys` and `aad` are HOST arrays (the sizes come from page
+ * headers the host parsed, the keys from its key retrieval); they are copied before the call returns,
+ * through growable pinned memory of the ctx, the keys as expanded schedules with H and its powers.
+ * Jobs are independent: they may share keys and come in any order. d_src and d_dst are 4-byte aligned;
+ * d_src is readable up to n_src rounded up to 4 and no load leaves that range.
+ * PQG_ERR_INVALID_ARG, before any launch: NULL ctx; n_jobs < 0; NULL jobs, d_src, d_dst, d_status or keys
+ * with n_jobs > 0; a job whose module leaves n_src, whose plaintext leaves n_dst or whose AAD leaves
+ * aad_bytes; an unknown mode, a key index outside keys, non-zero reserved; a key whose size is not 16, 24
+ * or 32 or whose bytes are all zero (AesCipher's constructor); more than 256 keys.
+ * Cost of the keys: a call whose keys or tile size differ from the previous call's builds every key's material on
+ * the host (the schedule and about tile / 16 + 200 products in GF(2^128): 1,200 at the default tile, well under a
+ * millisecond per key), and every call copies 4 (tile / 16) + 9,500 bytes per key (26 KB at the default tile)
+ * through pinned memory. The ctx keeps the last call's keys and material to compare and reuse; they are zeroed
+ * when replaced and by pqg_ctx_destroy.
+ * PQG_ERR_CORRUPT with st->page = the job: a module too short for a plaintext of 1 byte (the reference's
+ * "Wrong input length"). PQG_ERR_UNSUPPORTED: more than 2^28 tiles in one call. st may be NULL.
+ * n_jobs == 0 is valid and launches nothing. Launches: two (tiles, per-job fold), whatever n_jobs is. */
+int pqg_decrypt_pages(pqg_ctx* ctx, const uint8_t* d_src, uint64_t n_src, uint8_t* d_dst, uint64_t n_dst,
+                      const pqg_decrypt_job* jobs, int n_jobs, const pqg_aes_key* keys, int n_keys,
+                      const uint8_t* aad, uint64_t aad_bytes, int32_t* d_status, pqg_status* st);
+/* Synchronises the ctx stream and reads d_status back, like the codec *_sync calls: the first failing
+ * job is st->page, and the message of a mismatch contains "GCM tag check failed". */
+int pqg_decrypt_sync(pqg_ctx* ctx, const int32_t* d_status, int n_jobs, pqg_status* st);
+
+/* A compressed V2 page is one module over its levels and its compressed data (ColumnChunkPageReadStore.java:228):
+ * it is decrypted into the codec's source buffer, and its level bytes go on into the batch. pqg_copy_ranges copies
+ * n byte ranges of one device buffer into another in one launch (one wave per range). d_ranges is a DEVICE array,
+ * like the codec calls' job tables; a range that leaves n_src or n_dst, or has non-zero reserved, is skipped.
+ * Ranges must not overlap in d_dst. Asynchronous on the ctx stream. PQG_ERR_INVALID_ARG: NULL ctx, n < 0, NULL
+ * buffers or table with n > 0. n == 0 launches nothing. */
+typedef struct pqg_copy_range {     /* sizeof == 24 */
+  uint64_t src_offset;
+  uint64_t dst_offset;
+  uint32_t size;
+  uint32_t reserved;  /* 0 */
+} pqg_copy_range;
+int pqg_copy_ranges(pqg_ctx* ctx, const uint8_t* d_src, uint64_t n_src, uint8_t* d_dst, uint64_t n_dst,
+                    const pqg_copy_range* d_ranges, int n);
+
+/* Host only. AesCipher.createModuleAAD (AesCipher.java:72-117) for page modules: out <- file_aad ||
+ * module_type || row_group (2 bytes LE) || column (2 bytes LE) [|| page (2 bytes LE)], *out_len = its
+ * length. module_type is PQG_MODULE_DATA_PAGE (with the page ordinal) or PQG_MODULE_DICTIONARY_PAGE
+ * (without; `page` is ignored). PQG_ERR_INVALID_ARG: another module type, NULL out or out_len, NULL
+ * file_aad with a length, a negative ordinal, an ordinal above Short.MAX_VALUE (32767), or a capacity
+ * below the length (*out_len is still set). */
+int pqg_module_aad(const uint8_t* file_aad, uint32_t file_aad_length, int module_type, int row_group, int column,
+                   int page, uint8_t* out, uint32_t capacity, uint32_t* out_len);
 
 /* Human-readable name of an error code. */
 const char* pqg_error_name(int code);

@@ -62,6 +62,7 @@ const char* pqg_error_name(int code) {
     case PQG_ERR_NO_DICTIONARY: return "NO_DICTIONARY";
     case PQG_ERR_DICT_ENCODING: return "DICT_ENCODING";
     case PQG_ERR_CRC: return "CRC";
+    case PQG_ERR_TAG: return "TAG";
     default: return "UNKNOWN";
   }
 }
@@ -132,6 +133,10 @@ int pqg_ctx_set_dispatch(pqg_ctx* ctx, int key, int value) {
       if (value < 0 || !pqg::crc_tile_ok((uint32_t)value)) return PQG_ERR_INVALID_ARG;
       ctx->crc_tile = (uint32_t)value;
       return PQG_OK;
+    case PQG_DISPATCH_AES_TILE_BYTES:
+      if (value < 0 || !pqg::aes_tile_ok((uint32_t)value)) return PQG_ERR_INVALID_ARG;
+      ctx->aes_tile = (uint32_t)value;
+      return PQG_OK;
     default: return PQG_ERR_INVALID_ARG;
   }
 }
@@ -143,6 +148,7 @@ int pqg_ctx_destroy(pqg_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   if (c->last) pqg_plan_destroy(c->last);
+  c->aes_wipe_keys(true);  // pqg_decrypt_pages' copies of the callers' keys, on the host and on the device
   delete c;
   return PQG_OK;
 }

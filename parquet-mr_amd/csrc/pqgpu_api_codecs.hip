@@ -1,4 +1,5 @@
-// pqgpu_api_codecs.hip — the C ABI's work on compressed page bytes: page checksums (pqg_crc32_pages) and
+// pqgpu_api_codecs.hip — the C ABI's work on page bytes as they sit in the file: page checksums
+// (pqg_crc32_pages), decryption (pqg_decrypt_pages) and
 // the four decompressors (pqg_snappy_, pqg_lz4_raw_, pqg_gzip_, pqg_zstd_decompress), each with the
 // *_sync call that waits for the jobs and reports the first that failed.
 #include <hip/hip_runtime.h>
@@ -10,9 +11,9 @@
 #include "pqgpu_ctx.h"
 
 // The *_sync entry points: waits for the stream, reads the n_jobs status words and reports the first
-// non-zero one as job `page` of `what_job` (a PQG_ERR_CRC as what_crc, where given).
+// non-zero one as job `page` of `what_job` (a PQG_ERR_CRC as what_crc, a PQG_ERR_TAG as what_tag, where given).
 static int job_status_sync(pqg_ctx* ctx, const int32_t* d_status, int n_jobs, pqg_status* st, const char* what,
-                           const char* what_job, const char* what_crc = nullptr) {
+                           const char* what_job, const char* what_crc = nullptr, const char* what_tag = nullptr) {
   if (!ctx || n_jobs < 0) return PQG_ERR_INVALID_ARG;
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return PQG_ERR_HIP;
   if (st) set_status(st, PQG_OK, -1, -1, what);
@@ -22,7 +23,8 @@ static int job_status_sync(pqg_ctx* ctx, const int32_t* d_status, int n_jobs, pq
     return PQG_ERR_HIP;
   for (int j = 0; j < n_jobs; j++)
     if (h[(size_t)j]) {
-      set_status(st, h[(size_t)j], j, -1, h[(size_t)j] == PQG_ERR_CRC && what_crc ? what_crc : what_job);
+      set_status(st, h[(size_t)j], j, -1,
+                 h[(size_t)j] == PQG_ERR_CRC && what_crc ? what_crc : h[(size_t)j] == PQG_ERR_TAG && what_tag ? what_tag : what_job);
       return h[(size_t)j];
     }
   return PQG_OK;
@@ -70,6 +72,86 @@ int pqg_crc32_pages(pqg_ctx* ctx, const uint8_t* d_bytes, uint64_t n_bytes, cons
 int pqg_crc32_sync(pqg_ctx* ctx, const int32_t* d_status, int n_jobs, pqg_status* st) {
   return job_status_sync(ctx, d_status, n_jobs, st, "crc32", "crc32 job",
                          "could not verify page integrity, CRC checksum verification failed");
+}
+
+// ---- encrypted pages (pqgpu_aes_host.cpp validates and builds the tables, pqgpu_aes.hip runs) ---------
+static_assert(sizeof(pqg_decrypt_job) == 40 && sizeof(pqg_aes_key) == 36, "decrypt job layout");
+
+int pqg_decrypt_pages(pqg_ctx* ctx, const uint8_t* d_src, uint64_t n_src, uint8_t* d_dst, uint64_t n_dst,
+                      const pqg_decrypt_job* jobs, int n_jobs, const pqg_aes_key* keys, int n_keys,
+                      const uint8_t* aad, uint64_t aad_bytes, int32_t* d_status, pqg_status* st) {
+  if (st) { std::memset(st, 0, sizeof(*st)); st->page = -1; }
+  uint64_t n_tiles = 0, aad_blocks = 0;
+  int bad = -1;
+  const uint32_t T = ctx ? ctx->aes_tile : (uint32_t)PQG_AES_TILE_BYTES;
+  const int rc = pqg::aes_validate(ctx != nullptr, d_src, n_src, d_dst, n_dst, jobs, n_jobs, keys, n_keys, aad, aad_bytes,
+                                   d_status, T, &n_tiles, &aad_blocks, &bad);
+  if (rc != PQG_OK) {
+    set_status(st, rc, bad, -1, rc == PQG_ERR_CORRUPT ? "decrypt: Wrong input length" : "decrypt arguments");
+    return rc;
+  }
+  if (n_jobs == 0) return PQG_OK;
+  if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
+  if (!ctx->aes_te0.p) {  // (a pageable copy: done when it returns)
+    uint32_t te[256];
+    pqg::aes_te0(te);
+    if (ctx->aes_te0.ensure(sizeof(te)) != hipSuccess ||
+        hipMemcpy(ctx->aes_te0.p, te, sizeof(te), hipMemcpyHostToDevice) != hipSuccess) {
+      ctx->aes_te0.release();
+      return PQG_ERR_HIP;
+    }
+  }
+  const size_t key_words = pqg::aes_key_words(T);
+  const size_t keys_in = sizeof(pqg_aes_key) * (size_t)n_keys;
+  if (ctx->aes_keys_tile != T || ctx->aes_keys_seen.size() != keys_in ||
+      std::memcmp(ctx->aes_keys_seen.data(), keys, keys_in) != 0) {
+    ctx->aes_wipe_keys(false);
+    ctx->aes_keymat.assign(key_words * (size_t)n_keys, 0u);
+    for (int k = 0; k < n_keys; k++)
+      pqg::aes_build_key(keys[k].bytes, keys[k].size, T, ctx->aes_keymat.data() + key_words * (size_t)k);
+    ctx->aes_keys_seen.assign((const uint8_t*)keys, (const uint8_t*)keys + keys_in);
+    ctx->aes_keys_tile = T;
+  }
+  uint32_t slot;
+  if (!ctx->aes_ring.acquire(&slot)) return PQG_ERR_HIP;  // (waits for the fold of this slot AES_SLOTS calls ago)
+  // A failure below returns without publish(), as in pqg_crc32_pages: nothing that reads the slot was queued, so
+  // its event stays as it was (never recorded, or recorded behind work that has since run) and the next
+  // acquire() of the slot returns at once, which is right.
+  // jobs (64 bytes each), tiles (32), AAD blocks (16), key material (a multiple of 16): each part 16-byte aligned
+  const size_t job_bytes = sizeof(pqg::AesJobDev) * (size_t)n_jobs, tile_bytes = sizeof(pqg::AesTile) * (size_t)n_tiles;
+  const size_t aad_off = job_bytes + tile_bytes, key_off = aad_off + 16 * (size_t)aad_blocks;
+  const size_t bytes = key_off + 4 * key_words * (size_t)n_keys;
+  if (ctx->aes_pin[slot].cap < bytes && ctx->aes_pin[slot].ensure(bytes + bytes / 2) != hipSuccess) return PQG_ERR_HIP;
+  if (ctx->aes_dev[slot].cap < bytes && ctx->aes_dev[slot].ensure(bytes + bytes / 2) != hipSuccess) return PQG_ERR_HIP;
+  if (ctx->aes_partial[slot].cap < 16 * (size_t)n_tiles && ctx->aes_partial[slot].ensure(24 * (size_t)n_tiles) != hipSuccess)
+    return PQG_ERR_HIP;
+  uint8_t* pin = (uint8_t*)ctx->aes_pin[slot].p;
+  pqg::aes_build(jobs, n_jobs, aad, T, (pqg::AesJobDev*)pin, (pqg::AesTile*)(pin + job_bytes), pin + aad_off);
+  std::memcpy(pin + key_off, ctx->aes_keymat.data(), 4 * key_words * (size_t)n_keys);
+  if (hipMemcpyAsync(ctx->aes_dev[slot].p, pin, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return PQG_ERR_HIP;
+  const uint8_t* dev = (const uint8_t*)ctx->aes_dev[slot].p;
+  const hipError_t e = pqg::launch_decrypt(ctx->stream, d_src, n_src, d_dst, (const pqg::AesTile*)(dev + job_bytes),
+                                           (uint32_t)n_tiles, (const pqg::AesJobDev*)dev, (uint32_t)n_jobs, dev + aad_off,
+                                           (const uint32_t*)ctx->aes_te0.p, (const uint32_t*)(dev + key_off), T,
+                                           ctx->aes_partial[slot].p, d_status);
+  if (e != hipSuccess || !ctx->aes_ring.publish(slot, ctx->stream)) return PQG_ERR_HIP;
+  return PQG_OK;
+}
+
+int pqg_decrypt_sync(pqg_ctx* ctx, const int32_t* d_status, int n_jobs, pqg_status* st) {
+  return job_status_sync(ctx, d_status, n_jobs, st, "decrypt", "decrypt job", nullptr, "GCM tag check failed");
+}
+
+static_assert(sizeof(pqg_copy_range) == 24, "pqg_copy_range layout");
+
+int pqg_copy_ranges(pqg_ctx* ctx, const uint8_t* d_src, uint64_t n_src, uint8_t* d_dst, uint64_t n_dst,
+                    const pqg_copy_range* d_ranges, int n) {
+  if (!ctx || n < 0) return PQG_ERR_INVALID_ARG;
+  if (n == 0) return PQG_OK;
+  if (!d_src || !d_dst || !d_ranges) return PQG_ERR_INVALID_ARG;
+  if (hipSetDevice(ctx->device) != hipSuccess) return PQG_ERR_HIP;
+  const hipError_t e = pqg::launch_copy_ranges(ctx->stream, d_src, n_src, d_dst, n_dst, d_ranges, (uint32_t)n);
+  return e == hipSuccess ? PQG_OK : PQG_ERR_HIP;
 }
 
 static_assert(sizeof(pqg_snappy_job) == 24, "pqg_snappy_job layout");

@@ -13,6 +13,7 @@
 #include "pqgpu_api_host.h"
 #include "pqgpu_take.h"
 #include "pqgpu_crc.h"
+#include "pqgpu_aes.h"
 
 namespace pqg {
 
@@ -276,6 +277,33 @@ struct pqg_ctx {
   pqg::PinnedBuf crc_pin[CRC_SLOTS];
   pqg::DevBuf crc_dev[CRC_SLOTS], crc_partial[CRC_SLOTS];
   pqg::SlotRing<CRC_SLOTS> crc_ring;
+  // pqg_decrypt_pages: te0 on the device (built at the first call), and per slot the job, tile, AAD and key
+  // tables in growable pinned memory, their device copy and the tiles' GHASH partials (aes_ring, as above)
+  static constexpr int AES_SLOTS = 2;
+  uint32_t aes_tile = PQG_AES_TILE_BYTES;  // PQG_DISPATCH_AES_TILE_BYTES
+  pqg::DevBuf aes_te0;
+  pqg::PinnedBuf aes_pin[AES_SLOTS];
+  pqg::DevBuf aes_dev[AES_SLOTS], aes_partial[AES_SLOTS];
+  pqg::SlotRing<AES_SLOTS> aes_ring;
+  // the key material of the last call (pqg::aes_build_key), reused while the keys and the tile size stay;
+  // wiped when it is replaced and when the ctx goes (aes_wipe_keys, which also clears the pinned slots)
+  std::vector<uint8_t> aes_keys_seen;
+  uint32_t aes_keys_tile = 0;
+  std::vector<uint32_t> aes_keymat;
+  void aes_wipe_keys(bool slots) {
+    volatile uint8_t* p = aes_keys_seen.data();
+    for (size_t i = 0; i < aes_keys_seen.size(); i++) p[i] = 0;
+    volatile uint32_t* w = aes_keymat.data();
+    for (size_t i = 0; i < aes_keymat.size(); i++) w[i] = 0;
+    aes_keys_seen.clear();
+    aes_keymat.clear();
+    aes_keys_tile = 0;
+    for (int s = 0; slots && s < AES_SLOTS; s++) {
+      volatile uint8_t* q = (volatile uint8_t*)aes_pin[s].p;
+      for (size_t i = 0; q && i < aes_pin[s].cap; i++) q[i] = 0;
+      if (aes_dev[s].p) (void)hipMemset(aes_dev[s].p, 0, aes_dev[s].cap);
+    }
+  }
 };
 
 // pqg_decode on a batch whose readable bytes (n_bytes) reach past the caller's data (valid_bytes):

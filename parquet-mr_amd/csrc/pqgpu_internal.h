@@ -219,6 +219,17 @@ struct CrcJobDev;
 hipError_t launch_crc(hipStream_t st, const uint8_t* bytes, uint64_t n_bytes, const CrcTile* tiles, uint32_t n_tiles,
                       const CrcJobDev* jobs, uint32_t n_jobs, const uint32_t* tab, uint32_t tile_bytes,
                       uint32_t* partial, uint32_t* crc, int32_t* status);
+// pqgpu_aes.hip: pqg_decrypt_pages (AesTile, AesJobDev, the key material `keys` of tile_bytes: pqgpu_aes.h).
+// partial: 16 bytes per tile; k_aes_tiles, then k_aes_fold
+struct AesTile;
+struct AesJobDev;
+hipError_t launch_decrypt(hipStream_t st, const uint8_t* src, uint64_t n_src, uint8_t* dst, const AesTile* tiles,
+                          uint32_t n_tiles, const AesJobDev* jobs, uint32_t n_jobs, const uint8_t* aad,
+                          const uint32_t* te0, const uint32_t* keys, uint32_t tile_bytes, void* partial,
+                          int32_t* status);
+// pqgpu_aes.hip: pqg_copy_ranges, one wave per range (ranges outside the buffers are skipped)
+hipError_t launch_copy_ranges(hipStream_t st, const uint8_t* src, uint64_t n_src, uint8_t* dst, uint64_t n_dst,
+                              const pqg_copy_range* ranges, uint32_t n);
 hipError_t launch_unpack_runs(hipStream_t st, int w, const uint8_t* in, uint64_t in_bytes, const uint64_t* in_off,
                               const uint32_t* counts, const uint64_t* out_off, int32_t* out, int n_runs,
                               uint32_t max_count);

@@ -242,6 +242,7 @@ const char* pqg_java_exception(int code) {
     case PQG_ERR_DICT_ENCODING:
     case PQG_ERR_CRC:
       return "org/apache/parquet/io/ParquetDecodingException";
+    case PQG_ERR_TAG: return "org/apache/parquet/crypto/TagVerificationException";  // AesGcmDecryptor.decrypt
     case PQG_ERR_INVALID_ARG: return "java/lang/IllegalArgumentException";
     default:  // PQG_ERR_HIP, PQG_ERR_NO_DEVICE, PQG_ERR_TIMEOUT: the native backend failed, not the data
       return "java/lang/IllegalStateException";

@@ -44,6 +44,7 @@ ERR_CORRUPT = 18
 ERR_NO_DICTIONARY = 19
 ERR_DICT_ENCODING = 20
 ERR_CRC = 21
+ERR_TAG = 22  # TagVerificationException "GCM tag check failed"
 
 # ColumnMetaData.codec (parquet.thrift CompressionCodec; pqg_codec)
 CODEC_UNCOMPRESSED, CODEC_SNAPPY, CODEC_GZIP, CODEC_LZO, CODEC_BROTLI, CODEC_LZ4, CODEC_ZSTD, CODEC_LZ4_RAW = range(8)
@@ -57,7 +58,7 @@ ERROR_NAMES = {
     ERR_BIT_WIDTH: "BIT_WIDTH", ERR_DICT_ID: "DICT_ID", ERR_EMPTY_PAGE: "EMPTY_PAGE",
     ERR_EMPTY_PACKED_RUN: "EMPTY_PACKED_RUN", ERR_DELTA_CONFIG: "DELTA_CONFIG",
     ERR_DELTA_PAST_END: "DELTA_PAST_END", ERR_CORRUPT: "CORRUPT", ERR_NO_DICTIONARY: "NO_DICTIONARY",
-    ERR_DICT_ENCODING: "DICT_ENCODING", ERR_CRC: "CRC",
+    ERR_DICT_ENCODING: "DICT_ENCODING", ERR_CRC: "CRC", ERR_TAG: "TAG",
 }
 
 
@@ -223,6 +224,7 @@ DISPATCH_GZIP_PREPASS_MIN = 3  # pqg_gzip_decompress: smallest page (output byte
 DISPATCH_DICT_FUSED = 4  # dictionary pages: 1 = walk + expansion in one launch, 0 = two launches
 DISPATCH_TAKE_STAGED = 6  # pqg_take: 1 = kept elements staged in LDS and stored as aligned full-wave runs, 0 = one store per kept lane
 DISPATCH_ZSTD_PREPASS = 7  # pqg_zstd_decompress: 1 = sequence pre-pass + replay, 0 = every page through the inline decoder
+DISPATCH_AES_TILE_BYTES = 9  # pqg_decrypt_pages: ciphertext bytes one wave decrypts (a power of two, 1024 .. 32768)
 DISPATCH_CRC_TILE_BYTES = 8  # pqg_crc32_pages: bytes of a range one wave checksums (4096, 8192, 16384, 32768)
 DISPATCH_NULL_HINTS = 5  # V2 nullable columns: 1 = value kernels from the header null counts (verified), 0 = levels first
 
@@ -370,3 +372,28 @@ class CrcJob(C.Structure):
 
 CRC_JOB_DTYPE = np.dtype([("offset", "<u8"), ("size", "<u4"), ("expected", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 assert C.sizeof(CrcJob) == CRC_JOB_DTYPE.itemsize == 24
+
+# ---- encrypted pages (pqg_decrypt_pages) --------------------------------------------------------------
+AES_TILE_BYTES = 16384  # PQG_AES_TILE_BYTES
+DECRYPT_GCM, DECRYPT_CTR = 0, 1                      # pqg_decrypt_job.mode
+MODULE_DATA_PAGE, MODULE_DICTIONARY_PAGE = 2, 3      # ModuleCipherFactory.ModuleType
+AES_SIZE_LENGTH, AES_NONCE_LENGTH, AES_GCM_TAG_LENGTH = 4, 12, 16
+
+
+class DecryptJob(C.Structure):
+    """pqg_decrypt_job (40 bytes): one encrypted module of a device buffer."""
+    _fields_ = [("src_offset", C.c_uint64), ("dst_offset", C.c_uint64), ("src_size", C.c_uint32),
+                ("aad_offset", C.c_uint32), ("aad_length", C.c_uint32), ("mode", C.c_int32), ("key", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class AesKey(C.Structure):
+    """pqg_aes_key (36 bytes)."""
+    _fields_ = [("bytes", C.c_uint8 * 32), ("size", C.c_uint32)]
+
+
+DECRYPT_JOB_DTYPE = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("src_size", "<u4"), ("aad_offset", "<u4"),
+                              ("aad_length", "<u4"), ("mode", "<i4"), ("key", "<i4"), ("reserved", "<u4")])
+COPY_RANGE_DTYPE = np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"), ("size", "<u4"), ("reserved", "<u4")])  # pqg_copy_range
+AES_KEY_DTYPE = np.dtype([("bytes", "u1", (32,)), ("size", "<u4")])
+assert C.sizeof(DecryptJob) == DECRYPT_JOB_DTYPE.itemsize == 40 and C.sizeof(AesKey) == AES_KEY_DTYPE.itemsize == 36

@@ -27,6 +27,7 @@ class DeviceBatch:
         self.device = device
         self.bytes = torch.from_numpy(batch.data).to(device)
         self.codec_jobs = None  # [(codec, compressed blocks, job table, status, n)] when built by Decoder.upload_chunks
+        self.decrypt_jobs = None  # upload_chunks with encrypted chunks: what Decoder.decrypt_batch re-issues
 
     @property
     def n_bytes(self):
@@ -197,6 +198,73 @@ class Decoder:
                     f"chunk {ci}, page {k}: could not verify page integrity") + ", CRC checksum verification failed"
             raise native.PqgError(abi.ERR_CRC, what=what)
 
+    @staticmethod
+    def _key_table(keys):
+        table = np.zeros(len(keys), dtype=abi.AES_KEY_DTYPE)
+        for i, k in enumerate(keys):
+            k = bytes(k)
+            if len(k) > 32:
+                raise native.PqgError(abi.ERR_INVALID_ARG, what=f"AES key of {len(k)} bytes")
+            table["bytes"][i, :len(k)] = np.frombuffer(k, dtype=np.uint8)
+            table["size"][i] = len(k)
+        return table
+
+    def decrypt(self, d_src, d_dst, jobs, keys, aad=b"", d_status=None, sync=True):
+        """pqg_decrypt_pages: the encrypted modules (Parquet Modular Encryption page modules, as
+        BlockCipher.Encryptor wrote them) that `jobs` (a numpy array of abi.DECRYPT_JOB_DTYPE) locates in the
+        device uint8 tensor d_src are decrypted into the device uint8 tensor d_dst. keys: the key table (a list
+        of 16-, 24- or 32-byte keys the jobs index), aad: the host blob the jobs' aad_offset / aad_length refer to.
+        Returns (status_codes, status): per job OK or ERR_TAG, and pqg_decrypt_sync's status naming the first
+        failing job; with sync=False the call stays asynchronous and returns the device status tensor."""
+        n = len(jobs)
+        table = np.ascontiguousarray(jobs, dtype=abi.DECRYPT_JOB_DTYPE)
+        ktab = self._key_table(keys)
+        blob = np.frombuffer(bytes(aad), dtype=np.uint8)
+        if d_status is None:
+            d_status = torch.full((max(n, 1),), -1, dtype=torch.int32, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+        L = native.lib()
+        st = abi.Status()
+        rc = L.pqg_decrypt_pages(self.ctx, d_src.data_ptr(), d_src.numel(), d_dst.data_ptr(), d_dst.numel(),
+                                 table.ctypes.data if n else None, n, ktab.ctypes.data if len(ktab) else None, len(ktab),
+                                 blob.ctypes.data if blob.size else None, blob.size, d_status.data_ptr(), C.byref(st))
+        native.check(rc, st, what="pqg_decrypt_pages")
+        if not sync:
+            return d_status
+        st = abi.Status()
+        L.pqg_decrypt_sync(self.ctx, d_status.data_ptr(), n, C.byref(st))
+        return d_status[:n].cpu().numpy(), st
+
+    def decrypt_batch(self, dbatch):
+        """(Re)issue the page decryption of an upload_chunks batch on the decoder's stream (asynchronous, before
+        `decompress`): one pqg_decrypt_pages call per destination buffer (the batch, each codec's source buffer),
+        then the copy of the compressed V2 pages' levels from their codec's source buffer into the batch
+        (pqg_copy_ranges: one launch per codec, whatever the number of pages)."""
+        dj = getattr(dbatch, "decrypt_jobs", None)
+        if not dj:
+            return
+        for d_dst, table, d_status in dj["calls"]:
+            self.decrypt(dj["src"], d_dst, table, dj["keys"], dj["aad"], d_status=d_status, sync=False)
+        for d_from, d_ranges, n in dj["levels"]:
+            native.check(native.lib().pqg_copy_ranges(self.ctx, d_from.data_ptr(), d_from.numel(), dbatch.bytes.data_ptr(),
+                                                      dbatch.n_bytes, d_ranges.data_ptr(), n), what="pqg_copy_ranges")
+
+    def _decrypt_check(self, dbatch):
+        """Waits for decrypt_batch; raises PqgError(ERR_TAG) for the first failing module in chunk / page order."""
+        dj = dbatch.decrypt_jobs
+        bad = []
+        for (_, table, d_status), owners in zip(dj["calls"], dj["owners"]):
+            st = abi.Status()
+            rc = native.lib().pqg_decrypt_sync(self.ctx, d_status.data_ptr(), len(table), C.byref(st))
+            if rc not in (abi.OK, abi.ERR_TAG):
+                native.check(rc, st, what="pqg_decrypt_pages")
+            if rc == abi.ERR_TAG:
+                bad += [owners[i] for i in np.flatnonzero(d_status[:len(table)].cpu().numpy())]
+        if bad:
+            ci, k = min(bad)
+            what = f"chunk {ci}, dictionary page" if k < 0 else f"chunk {ci}, page {k}"
+            raise native.PqgError(abi.ERR_TAG, what=what + ": GCM tag check failed")
+
     def upload_chunks(self, chunks, verify_crc=False):
         """Column chunks whose pages may be SNAPPY-, GZIP-, ZSTD- or LZ4_RAW-compressed -> a DeviceBatch of
         uncompressed pages.
@@ -213,35 +281,67 @@ class Decoder:
         the codec kernels (pqg_snappy / zstd / lz4_raw / gzip_decompress) write every block straight into its page's
         place in the batch on the GPU (ColumnChunkPageReadStore.readPage's decompress step).
         Raises PqgError(CORRUPT / EOF) with the failing block when a block is malformed or its
-        length differs from the header."""
+        length differs from the header.
+
+        A chunk with `decryption` set (crypto.ColumnDecryption) holds encrypted page modules: every `pg.body` and
+        `ch.dict_page` is [length][nonce][ciphertext][tag] (GCM) or [length][nonce][ciphertext] (CTR) around the
+        bytes described above (a V2 page is one module over its levels and its data,
+        ColumnChunkPageReadStore.java:228). The modules are uploaded once and decrypted on the device
+        (pqg_decrypt_pages) to where the next step reads them: an uncompressed page into its place in the batch, a
+        compressed one into its codec's source buffer (a V2 page's levels go on from there into the batch). A page's
+        ordinal in its AAD is its index in the chunk unless the page carries `page_ordinal`. A module whose tag
+        does not verify raises PqgError(ERR_TAG) naming the chunk and the page, before any codec's outcome.
+        verify_crc together with an encrypted chunk is refused (ERR_UNSUPPORTED). Chunks without `decryption`
+        are laid out, checksummed and decompressed as without this feature; decryption is one more optional step
+        between the checksums and the codecs."""
         import copy
-        # (codec, payload, ("dict", chunk) | ("page", page index), prefix, levels kept before the payload in
-        #  the codec source, (crc, (chunk, page | -1)) | None)
+        encrypted = any(getattr(ch, "decryption", None) is not None for ch in chunks)
+        if encrypted and verify_crc:
+            raise native.PqgError(abi.ERR_UNSUPPORTED, what="verify_crc with encrypted chunks")
+        # per block: (codec, compressed payload (its size when the page is encrypted), ("dict", chunk) | ("page", page
+        #  index), levels kept before the payload in the codec source (zeros when encrypted), bytes of the page before
+        #  the payload's output, (crc, (chunk, page | -1)) | None, module | None)
+        # module = (module bytes, decryption, AAD, (chunk, page | -1))
         placeholders, blocks = [], []
         plain_crcs = []                 # uncompressed pages with a crc: (("dict", chunk) | ("page", page index), crc, key)
+        direct = []                     # uncompressed encrypted pages: (("dict", chunk) | ("page", page index), module)
         n_page = 0
         for ci, ch in enumerate(chunks):
+            dec = getattr(ch, "decryption", None)
+            over = dec.overhead() if dec is not None else 0
             ph = copy.copy(ch)
             ph.pages = []
             dcrc = ch.dict_crc if verify_crc else None
-            if ch.dict_page is not None and ch.dict_codec != batch.UNCOMPRESSED:
-                if ch.dict_codec not in self._CODEC_FN:
-                    raise native.PqgError(abi.ERR_UNSUPPORTED, what=f"dictionary page codec {ch.dict_codec}")
-                ph.dict_page = bytes(ch.dict_uncompressed_size)
-                blocks.append((ch.dict_codec, ch.dict_page, ("dict", len(placeholders)), 0, b"",
-                               None if dcrc is None else (dcrc, (ci, -1))))
-            elif ch.dict_page is not None and dcrc is not None:
-                plain_crcs.append((("dict", len(placeholders)), dcrc, (ci, -1)))
+            if ch.dict_page is not None:
+                mod = None if dec is None else (bytes(ch.dict_page), dec, dec.dictionary_aad(), (ci, -1))
+                n_plain = max(len(ch.dict_page) - over, 0)
+                if ch.dict_codec != batch.UNCOMPRESSED:
+                    if ch.dict_codec not in self._CODEC_FN:
+                        raise native.PqgError(abi.ERR_UNSUPPORTED, what=f"dictionary page codec {ch.dict_codec}")
+                    ph.dict_page = bytes(ch.dict_uncompressed_size)
+                    blocks.append((ch.dict_codec, n_plain if mod else ch.dict_page, ("dict", len(placeholders)), b"", 0,
+                                   None if dcrc is None else (dcrc, (ci, -1)), mod))
+                elif mod:
+                    ph.dict_page = bytes(n_plain)
+                    direct.append((("dict", len(placeholders)), mod))
+                elif dcrc is not None:
+                    plain_crcs.append((("dict", len(placeholders)), dcrc, (ci, -1)))
             for k, pg in enumerate(ch.pages):
                 q = copy.copy(pg)
                 crc = pg.crc if verify_crc else None
+                mod = None if dec is None else (bytes(pg.body), dec, dec.page_aad(getattr(pg, "page_ordinal", k)), (ci, k))
+                n_plain = max(len(pg.body) - over, 0)
                 if pg.codec in self._CODEC_FN:
                     lv = pg.rl_byte_length + pg.dl_byte_length if pg.version == 2 else 0
-                    q.body = pg.body[:lv] + bytes(pg.uncompressed_size - lv)
-                    blocks.append((pg.codec, pg.body[lv:], ("page", n_page), lv, b"" if crc is None else pg.body[:lv],
-                                   None if crc is None else (crc, (ci, k))))
+                    q.body = (bytes(lv) if mod else pg.body[:lv]) + bytes(pg.uncompressed_size - lv)
+                    levels = bytes(lv) if mod else pg.body[:lv] if crc is not None else b""
+                    blocks.append((pg.codec, max(n_plain - lv, 0) if mod else pg.body[lv:], ("page", n_page), levels, lv,
+                                   None if crc is None else (crc, (ci, k)), mod))
                 elif pg.codec != batch.UNCOMPRESSED:
                     raise native.PqgError(abi.ERR_UNSUPPORTED, what=f"page codec {pg.codec}")
+                elif mod:
+                    q.body = bytes(n_plain)
+                    direct.append((("page", n_page), mod))
                 elif crc is not None:
                     plain_crcs.append((("page", n_page), crc, (ci, k)))
                 ph.pages.append(q)
@@ -254,48 +354,85 @@ class Decoder:
         for i, ch in enumerate(placeholders):
             seen.setdefault(getattr(ch, "column_index", i), len(seen))
             col_of_chunk.append(seen[getattr(ch, "column_index", i)])
+
+        def place(kind, idx):
+            if kind == "dict":
+                c = hb.columns[col_of_chunk[idx]]
+                return int(c["dict_offset"]), int(c["dict_size"])
+            return int(hb.pages["offset"][idx]), int(hb.pages["size"][idx])
+
+        # the encrypted modules, uploaded once; the key table and the AAD blob of the decrypt calls
+        enc, keys, key_of, aads = [], [], {}, []
+        enc_pos = aad_pos = 0
+
+        def job(mod, dst_offset):
+            nonlocal enc_pos, aad_pos
+            data, dec, aad, owner = mod
+            if dec.key not in key_of:
+                key_of[dec.key] = len(keys)
+                keys.append(dec.key)
+            row = (enc_pos, dst_offset, len(data), aad_pos, len(aad), dec.mode, key_of[dec.key], 0)
+            enc.append(data)
+            aads.append(aad)
+            enc_pos += len(data)
+            aad_pos += len(aad)
+            return row, owner
+
+        calls = []                      # decrypt calls: (destination tensor, [(row, owner)])
+        if direct:
+            calls.append((dbatch.bytes, [job(mod, place(kind, idx)[0]) for (kind, idx), mod in direct]))
         crc_buffers = []                # [(device tensor, [(offset, size, crc, key)])]
         if plain_crcs:
-            jobs = []
-            for (kind, idx), crc, key in plain_crcs:
-                if kind == "dict":
-                    jobs.append((int(hb.columns[col_of_chunk[idx]]["dict_offset"]), len(placeholders[idx].dict_page), crc, key))
-                else:
-                    jobs.append((int(hb.pages["offset"][idx]), int(hb.pages["size"][idx]), crc, key))
-            crc_buffers.append((dbatch.bytes, jobs))
-        if not blocks:
-            self._verify_crc(crc_buffers)
-            return dbatch
-        jobsets = []
+            crc_buffers.append((dbatch.bytes, [place(kind, idx) + (crc, key) for (kind, idx), crc, key in plain_crcs]))
+        jobsets, level_copies = [], []
         for codec in sorted({b[0] for b in blocks}):
             mine = [b for b in blocks if b[0] == codec]
             src, pos = [], 0
             table = np.zeros(len(mine), dtype=np.dtype([("src_offset", "<u8"), ("dst_offset", "<u8"),
                                                         ("src_size", "<u4"), ("dst_size", "<u4")]))
-            crc_jobs = []
-            for j, (_, payload, (kind, idx), prefix, levels, crc) in enumerate(mine):
-                if kind == "dict":
-                    dst = int(hb.columns[col_of_chunk[idx]]["dict_offset"])
-                    n_out = int(hb.columns[col_of_chunk[idx]]["dict_size"])
-                else:
-                    dst = int(hb.pages["offset"][idx]) + prefix
-                    n_out = int(hb.pages["size"][idx]) - prefix
-                # a checksummed V2 page: its levels sit right before the payload, which stays 16-byte aligned
+            crc_jobs, rows, lv_rows = [], [], []
+            for j, (_, payload, (kind, idx), levels, prefix, crc, mod) in enumerate(mine):
+                dst, n_out = place(kind, idx)
+                n_pay = payload if mod else len(payload)
+                # a checksummed or encrypted V2 page: its levels sit right before the payload, which stays 16-byte aligned
                 front = bytes((-len(levels)) % 16) + levels
                 if crc is not None:
-                    crc_jobs.append((pos + len(front) - len(levels), len(levels) + len(payload), crc[0], crc[1]))
-                table[j] = (pos + len(front), dst, len(payload), n_out)
-                src.append(front + payload + bytes((-len(payload)) % 16))
+                    crc_jobs.append((pos + len(front) - len(levels), len(levels) + n_pay, crc[0], crc[1]))
+                if mod:
+                    rows.append(job(mod, pos + len(front) - len(levels)))
+                    if levels:
+                        lv_rows.append((pos + len(front) - len(levels), dst, len(levels), 0))
+                table[j] = (pos + len(front), dst + prefix, n_pay, n_out - prefix)
+                src.append(front + (bytes(n_pay) if mod else payload) + bytes((-n_pay) % 16))
                 pos += len(src[-1])
             d_src = torch.from_numpy(np.frombuffer(b"".join(src) + bytes(16), dtype=np.uint8).copy()).to(self.device)
             d_jobs = torch.from_numpy(table.view(np.uint8).copy()).to(self.device)
             d_status = torch.zeros(len(mine), dtype=torch.int32, device=self.device)
             jobsets.append((codec, d_src, d_jobs, d_status, len(mine)))
             crc_buffers.append((d_src, crc_jobs))
+            if rows:
+                calls.append((d_src, rows))
+            if lv_rows:
+                ranges = np.array(lv_rows, dtype=abi.COPY_RANGE_DTYPE)
+                level_copies.append((d_src, torch.from_numpy(ranges.view(np.uint8).copy()).to(self.device), len(lv_rows)))
+        if calls:
+            d_enc = torch.from_numpy(np.frombuffer(b"".join(enc) + bytes(16), dtype=np.uint8).copy()).to(self.device)
+            dbatch.decrypt_jobs = {
+                "src": d_enc, "keys": keys, "aad": b"".join(aads), "levels": level_copies,
+                "calls": [(d_dst, np.array([r for r, _ in rows], dtype=abi.DECRYPT_JOB_DTYPE),
+                           torch.full((len(rows),), -1, dtype=torch.int32, device=self.device)) for d_dst, rows in calls],
+                "owners": [[o for _, o in rows] for _, rows in calls]}
+        if not blocks and not calls:
+            self._verify_crc(crc_buffers)
+            return dbatch
         torch.cuda.current_stream(self.device).synchronize()  # the uploads above, before the decoder's stream
         self._verify_crc(crc_buffers)  # before the codecs' outcome: the reference throws in readAllPages
-        dbatch.codec_jobs = jobsets
-        self.decompress(dbatch)
+        if calls:
+            self.decrypt_batch(dbatch)
+            self._decrypt_check(dbatch)  # likewise: the reference decrypts before it decompresses
+        if jobsets:
+            dbatch.codec_jobs = jobsets
+            self.decompress(dbatch)
         for codec, _, _, d_status, n in jobsets:
             st = abi.Status()
             _, sync, what = self._CODEC_FN[codec]

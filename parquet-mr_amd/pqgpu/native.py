@@ -44,6 +44,8 @@ EXPORTS = [
     "pqg_take_records",
     # page checksums on the device, and their host helpers
     "pqg_crc32_pages", "pqg_crc32_sync", "pqg_crc32_combine", "pqg_crc_jobs_from_headers",
+    # encrypted pages on the device, and the module AAD
+    "pqg_decrypt_pages", "pqg_decrypt_sync", "pqg_module_aad", "pqg_copy_ranges",
     # row-group dictionary filter (DictionaryFilter.canDrop for every row group of a file)
     "pqg_filter_row_groups", "pqg_chunk_has_non_dictionary_pages", "pqg_decode_dictionaries",
 ]
@@ -129,6 +131,12 @@ def lib():
         L.pqg_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, u64]
         L.pqg_crc32_combine.restype = C.c_uint32
         L.pqg_crc_jobs_from_headers.argtypes = [vp, i32, u64, vp, vp, i32, C.POINTER(i32), C.POINTER(abi.Status)]
+        L.pqg_decrypt_pages.argtypes = [vp, vp, u64, vp, u64, vp, i32, vp, i32, vp, u64, vp, C.POINTER(abi.Status)]
+        L.pqg_decrypt_sync.argtypes = [vp, vp, i32, C.POINTER(abi.Status)]
+        L.pqg_copy_ranges.argtypes = [vp, vp, u64, vp, u64, vp, i32]
+        L.pqg_module_aad.argtypes = [vp, C.c_uint32, i32, i32, i32, i32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.pqg_java_exception.argtypes = [i32]
+        L.pqg_java_exception.restype = C.c_char_p
         L.pqg_decode_dictionaries.argtypes = [vp, vp, u64, vp, i32, C.POINTER(abi.Status)]
         L.pqg_filter_row_groups.argtypes = [vp, vp, vp, i32, u64, vp, vp, u64, vp]
         L.pqg_chunk_has_non_dictionary_pages.argtypes = [vp, i32, vp, i32]
